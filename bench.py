@@ -18,6 +18,13 @@ allreduce, hipGraph-captured decode) => strong scaling.
 
 One timed "step" = one continuous-batching decode iteration over the
 steady-state batch (BATCH sequences), i.e. BATCH new tokens per GPU.
+
+A plain run does only what the headline figure needs: build the engine,
+prefill, warm up, time --steps decode iterations, print one JSON line.
+--dump-outputs DIR additionally writes what the last timed step returned
+(see OutputTap.dump). --full is where measurements beyond the headline
+belong; there are none today, so it changes nothing (the co-resident
+configuration stays behind its own --coresident switch).
 """
 from __future__ import annotations
 
@@ -27,7 +34,80 @@ import os
 import statistics
 import time
 
+import numpy as np
 import torch
+
+DUMP_LOGITS_BYTES = 32 << 20    # cap for one dumped logits sample (fp32)
+
+
+def build_model(name: str, device: str, seed: int,
+                tp_size: int = 1, tp_rank: int = 0):
+    """The model LLMEngine would build for itself, bit for bit, but
+    allocated on the GPU from the start. The engine's own path
+    default-initialises 8B fp32 parameters on the host before
+    init_random() overwrites them on the device, which costs ~30 s per
+    run that no figure needs. The cast/move sequence is the engine's, so
+    the RoPE table (always computed on the host) and the seeded weights
+    come out identical."""
+    from helix_amd.models.llama import LlamaForCausalLM, PRESETS
+    with torch.device(device):
+        model = LlamaForCausalLM(PRESETS[name], tp_size, tp_rank)
+    model = model.to(torch.bfloat16).to(device)
+    model.init_random(seed)
+    torch.cuda.empty_cache()        # hand back the fp32 staging copy
+    return model
+
+
+class OutputTap:
+    """Keeps hold of what an engine's latest step() produced so that
+    --dump-outputs can write it once the timed loop is over. Nothing is
+    copied while steps are being timed: the tap only keeps a reference
+    to the logits tensor the sampler was handed."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.events = []
+        self.logits = None
+        inner = eng._sample
+
+        def tapped(batch, logits):
+            self.logits = logits
+            return inner(batch, logits)
+        eng._sample = tapped
+
+    def dump(self, out_dir: str, suffix: str = "") -> None:
+        """Write the last step's results as float .npy files:
+
+        tokens<suffix>.npy       float64 [n_requests]: the token id the
+                                 step returned for request i (-1: none)
+        logits<suffix>.npy       float32 [n_requests, C]: the logits row
+                                 each of those tokens was sampled from
+                                 (NaN row: none); all V columns when that
+                                 fits DUMP_LOGITS_BYTES, else a fixed
+                                 seed-0 sample of C columns
+        logits_cols<suffix>.npy  float64 [C]: the vocab column indices
+        """
+        os.makedirs(out_dir, exist_ok=True)
+        n = len(self.eng.seqs)
+        # request ids are "<prefix>-<i>"; index by i so the file layout
+        # does not depend on scheduling order
+        idx = [int(seq.seq_id.rsplit("-", 1)[1]) for seq, _, _ in self.events]
+        tokens = np.full(n, -1.0, dtype=np.float64)
+        tokens[idx] = [tok for _, tok, _ in self.events]
+        np.save(os.path.join(out_dir, f"tokens{suffix}.npy"), tokens)
+        if self.logits is None or not idx:
+            return
+        V = self.logits.shape[1]
+        ncols = min(V, max(1, DUMP_LOGITS_BYTES // (4 * n)))
+        cols = np.arange(V) if ncols == V else np.sort(
+            np.random.default_rng(0).choice(V, ncols, replace=False))
+        sel = torch.from_numpy(cols).to(self.logits.device)
+        rows = self.logits[:len(idx)].index_select(1, sel).float().cpu()
+        logits = np.full((n, ncols), np.nan, dtype=np.float32)
+        logits[idx] = rows.numpy()
+        np.save(os.path.join(out_dir, f"logits{suffix}.npy"), logits)
+        np.save(os.path.join(out_dir, f"logits_cols{suffix}.npy"),
+                cols.astype(np.float64))
 
 
 def run_coresident(args) -> None:
@@ -51,7 +131,8 @@ def run_coresident(args) -> None:
                            eos_token_id=-1, seed=0,
                            kv_cache_blocks=blocks(bsz),
                            kv_cache_dtype=args.kv_dtype)
-        engines.append(LLMEngine(cfg, device=device))
+        engines.append(LLMEngine(cfg, device=device,
+                                 model=build_model(model, device, cfg.seed)))
     bge = EmbeddingInstance(DEFAULT_SPECS["bge-base"], device)
     emb_texts = [f"document {i} about GPUs, HBM and xGMI topology" * 4
                  for i in range(16)]
@@ -80,6 +161,7 @@ def run_coresident(args) -> None:
                                 (bsz, args.prompt_len)).tolist()
         for i, p in enumerate(prompts):
             eng.add_request(f"bench-{eng.cfg.model}-{i}", p, sp)
+    taps = [OutputTap(eng) for eng in engines] if args.dump_outputs else []
 
     t0 = time.monotonic()
     for eng in engines:
@@ -94,17 +176,20 @@ def run_coresident(args) -> None:
     def one_step():
         with torch.cuda.stream(emb_stream):
             bge.model(emb_ids, emb_cu, emb_maxlen)
-        for eng in engines:
-            eng.step()
+        return [eng.step() for eng in engines]
 
     for _ in range(args.warmup):
         one_step()
     torch.cuda.synchronize()
     t0 = time.monotonic()
+    events = [[] for _ in engines]
     for _ in range(args.steps):
-        one_step()
+        events = one_step()
     torch.cuda.synchronize()
     elapsed = time.monotonic() - t0
+    for tap, ev in zip(taps, events):
+        tap.events = ev
+        tap.dump(args.dump_outputs, suffix=f"_{tap.eng.cfg.model}")
 
     tokens = (b1 + b2) * args.steps
     print(json.dumps({
@@ -158,6 +243,12 @@ def main():
                     help="fp8: e4m3 KV cache (opt-in)")
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "tokens and logits to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none at present)")
     args = ap.parse_args()
 
     if args.coresident:
@@ -207,9 +298,12 @@ def main():
         ar_ok = parallel.init_custom_allreduce(
             max(8 << 20, args.batch * hidden * 2))
         cfg.enforce_eager = not ar_ok
-        eng = LLMEngine(cfg, device=device, tp_size=world, tp_rank=rank)
+        eng = LLMEngine(cfg, device=device, tp_size=world, tp_rank=rank,
+                        model=build_model(args.model, device, cfg.seed,
+                                          world, rank))
     else:
-        eng = LLMEngine(cfg, device=device)
+        eng = LLMEngine(cfg, device=device,
+                        model=build_model(args.model, device, cfg.seed))
 
     torch.manual_seed(1234 + (0 if tp else rank))
     vocab = eng.model_cfg.vocab_size
@@ -219,6 +313,7 @@ def main():
                         max_tokens=10 ** 9, ignore_eos=True)
     for i, p in enumerate(prompts):
         eng.add_request(f"bench-{i}", p, sp)
+    tap = OutputTap(eng) if args.dump_outputs and rank == 0 else None
 
     # Prefill (untimed) — also yields TTFT for every request.
     t0 = time.monotonic()
@@ -238,11 +333,15 @@ def main():
         dist.barrier()
 
     # Timed region: exactly --steps decode iterations.
+    events = []
     t0 = time.monotonic()
     for _ in range(args.steps):
-        eng.step()
+        events = eng.step()
     torch.cuda.synchronize()
     elapsed = time.monotonic() - t0
+    if tap is not None:
+        tap.events = events
+        tap.dump(args.dump_outputs)
     if distributed:
         dist.barrier()
         t = torch.tensor([elapsed], device=device)

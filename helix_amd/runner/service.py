@@ -453,7 +453,11 @@ class RunnerService:
                 inst = ImageGenInstance(spec, self.device)
             elif spec.tp > 1:
                 from helix_amd.runner.tp_instance import TPLLMInstance
-                inst = TPLLMInstance(spec, spec.tp)
+                # workers follow the service's device: a CPU service on a
+                # host that happens to have one GPU must not ask for tp GPUs
+                inst = TPLLMInstance(
+                    spec, spec.tp,
+                    device_type=torch.device(self.device).type)
             else:
                 inst = LLMInstance(spec, self.device)
             log.info("loaded %s in %.1fs", model, time.time() - t0)
