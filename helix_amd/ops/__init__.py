@@ -177,8 +177,9 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             window, cu_seqlens_k)
 
 
-# Flash-decoding split-K quantum (must match PART_QUANT in
-# paged_attn_decode.hip).
+# Flash-decoding split-K quantum: PART_QUANT in paged_attn_decode.hip,
+# which the extension exports as _C.DECODE_PART_QUANT (a test holds the
+# two equal).
 DECODE_PARTITION = 128
 
 

@@ -27,8 +27,9 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
                        torch::Tensor k_cache, torch::Tensor v_cache,
                        torch::Tensor block_tables, torch::Tensor seq_lens,
                        double scale, torch::Tensor tmp_out,
-                       torch::Tensor tmp_ml, int64_t partition_size,
+                       torch::Tensor tmp_ml, int64_t max_len,
                        int64_t window);
+int64_t decode_part_quant();
 void attn_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k,
                   torch::Tensor v, torch::Tensor cu_seqlens,
                   torch::Tensor cu_seqlens_k, int64_t max_seqlen,
@@ -76,6 +77,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Scatter K/V rows into paged cache");
   m.def("paged_attn_decode", &paged_attn_decode,
         "Paged decode attention (GQA, flash-decoding partitions)");
+  m.attr("DECODE_PART_QUANT") = decode_part_quant();
   m.def("attn_prefill", &attn_prefill,
         "Varlen causal flash prefill attention (MFMA)");
   m.def("sample_tokens", &sample_tokens, "Greedy/Gumbel token sampling");

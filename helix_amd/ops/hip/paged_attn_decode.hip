@@ -3,21 +3,37 @@
 // Replaces the decode attention the reference delegates to vLLM
 // (SURVEY.md §2.8 "Decode attention (paged KV)").
 //
-// Design (MI355X-first, v3 — templated + load-batched):
+// Design:
 //  - KV-bandwidth-bound: each KV byte is read once per kv-head and
 //    amortized across the G = Hq/Hkv GQA query heads.
 //  - grid = (num_seqs, Hkv, num_partitions): flash-decoding split-K, host
-//    sizes partitions to fill the 256 CUs (>= ~1024 workgroups).
+//    sizes partitions to fill the 256 CUs (>= TARGET_WGS workgroups, at
+//    most MAX_PARTS partitions); a reduce kernel merges the partials.
 //  - DHEAD and G are template parameters so every inner loop fully
 //    unrolls; K rows and V tiles are loaded into registers in batches
-//    BEFORE any math so the wave keeps many VMEM ops in flight (v2's
-//    runtime-D loops serialized load->use and reached only 0.5 TB/s —
-//    profiles/r01_decode_profile_v1.md).
+//    BEFORE any math so the wave keeps many VMEM ops in flight.
 //  - 128-thread blocks (2 waves) walk the partition in 128-token chunks:
-//      A: thread t loads K row of token t (DHEAD/8 x 16B batched), dots
-//         against the G query vectors in LDS (broadcast reads).
+//      A: thread t dots the K row of token t (16B loads issued one chunk
+//         ahead, see kpre below) against the G query vectors in LDS
+//         (broadcast reads).
 //      B: per-head online softmax (running m, l), one wave per head.
-//      C: V accumulation, thread owns a dim pair, 8-token load batches.
+//      C: V accumulation, thread owns 8 dims, VPS-token load batches
+//         (bf16 rows staged raw, fp8 rows converted as they land).
+//  - KV8: the paged cache holds OCP e4m3 bytes (opt-in
+//    kv_cache_dtype="fp8"): halves the KV traffic this kernel is
+//    latency/BW-bound on; dequant is one v_cvt per element.
+//  - launch bounds floor of 2 waves/SIMD: register room for the 16-deep
+//    K prefetch (168 VGPRs, no spills, still 3 waves/SIMD).
+//
+// Retired variants, all measured slower; the last commit that holds
+// them is named in profiles/r03_decode_prune.md:
+//  - MFMA phase A (16x16x32 bf16 scores): -20 %, docs/KERNELS.md and
+//    profiles/r01_pmc_decode_b512.txt (latency-bound, not VALU-bound).
+//  - K prefetch without the waves/SIMD floor of 2: -3 % on the
+//    microbench, profiles/r02_decode_kpre.md (compiler re-sinks it).
+//  - waves/SIMD floor of 2 without K prefetch: +-0, same file.
+//  - V prefetch across chunks: 202 VGPRs, occupancy 3 -> 2, -7 % e2e,
+//    same file.
 #include "common.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -29,30 +45,38 @@ namespace {
 constexpr int NTHREADS = 128;
 constexpr int CHUNK = 128;
 constexpr int MAX_G = 8;
-constexpr int PART_QUANT = 128;
+constexpr int PART_QUANT = 128;   // split-K partition sizes are multiples
+constexpr int MAX_PARTS = 512;    // weights the reduce kernel holds in LDS
+constexpr int TARGET_WGS = 1024;  // split-K until the grid is this large
 
-// MFMA_A: phase A computes scores with f32_16x16x32_bf16 matrix ops
-// (16 tokens x G queries per instruction) instead of per-thread VALU
-// dots — motivated by the B=512 PMC: 37 VALU per vector load and
-// wait:busy 14:1 (profiles/r01_pmc_decode_b512.txt).
-// KV8: the paged cache holds OCP e4m3 bytes (opt-in
-// kv_cache_dtype="fp8"): halves the KV traffic this kernel is
-// latency/BW-bound on; dequant is one v_cvt per element in the math
-// loops. MFMA_A and KV8 are mutually exclusive instantiations.
-// VPS: phase-C V rows staged RAW (u16x8) per batch — the round-2
-// deep-pipelining lever (PMC wait:busy 14:1, latency-bound): more V
-// bytes in flight per wave before any conversion VALU touches them.
-// OCC: launch_bounds waves/SIMD floor override (0 = round-1 default).
-// KPRE: inter-chunk K prefetch. The r2 ISA audit (profiles/
-// r02_decode_kpre.md) showed the compiler sinking phase A's 16-deep raw
-// K staging into the consume loop — steady state s_waitcnt vmcnt(1),
-// i.e. only ~2 VMEM loads in flight per wave, matching the 14:1
-// wait:busy PMC. KPRE hoists the next chunk's 16 b128 K loads to just
-// after the current chunk's scores are consumed, so they land during
-// phases B+C (softmax + V) instead of head-of-line blocking phase A.
-template <int DHEAD, int G, bool MFMA_A, bool KV8, int VPS = 4, int OCC = 0,
-          bool KPRE = false>
-__global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void paged_attn_decode_kernel(
+// How a cache of each type is read: 16-byte K-row vectors, 8-element
+// V vectors, and the widen to fp32.
+template <bool KV8> struct CacheElem;
+template <> struct CacheElem<false> {
+  using elem = uint16_t;
+  using kvec = u16x8;
+  using vvec = u16x8;
+  static constexpr int KVEC = 8;
+  static __device__ __forceinline__ float to_f32(uint16_t x) {
+    return bf16_to_f32(x);
+  }
+};
+template <> struct CacheElem<true> {
+  using elem = uint8_t;
+  using kvec = u8x16;
+  using vvec = u8x8;
+  static constexpr int KVEC = 16;
+  static __device__ __forceinline__ float to_f32(uint8_t x) {
+    return fp8_to_f32(x);
+  }
+};
+
+// VPS: phase-C V rows loaded per batch. bf16 rows are staged raw, so
+// more V bytes are in flight per wave before any conversion VALU
+// touches them: 4 on a full grid, 8 when the grid underfills the chip
+// (see launch_decode). fp8 does not stage raw and is built with 4 only.
+template <int DHEAD, int G, bool KV8, int VPS>
+__global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
     uint16_t* __restrict__ out,          // [B, Hq, D] (used when nparts==1)
     float* __restrict__ tmp_out,         // [B, Hq, maxP, D]
     float* __restrict__ tmp_ml,          // [B, Hq, maxP, 2]
@@ -63,6 +87,12 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
     const int* __restrict__ seq_lens,    // [B]
     float scale, int Hkv, int block_size, int max_blocks,
     int partition_size, int max_parts, int window) {
+  using CE = CacheElem<KV8>;
+  using elem_t = typename CE::elem;
+  using kvec_t = typename CE::kvec;
+  using vvec_t = typename CE::vvec;
+  constexpr int KVEC = CE::KVEC;
+
   const int seq = blockIdx.x;
   const int hkv = blockIdx.y;
   const int part = blockIdx.z;
@@ -102,24 +132,6 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
   }
   __syncthreads();
 
-  // Q fragments for the MFMA path: A[row=query g][k=dim], rows >= G
-  // zero.  Lane holds A[lane&15][(lane>>4)*8+i] per 32-dim step.
-  constexpr int NKK = DHEAD / 32;
-  bf16x8 qfrag[MFMA_A ? NKK : 1];
-  if constexpr (MFMA_A) {
-    const int l_lo = threadIdx.x & 15;
-    const int l_hi = (threadIdx.x & (WAVE - 1)) >> 4;
-#pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float qv = (l_lo < G)
-            ? q_lds[l_lo][kk * 32 + l_hi * 8 + i] : 0.f;
-        reinterpret_cast<uint16_t*>(&qfrag[kk])[i] = f32_to_bf16(qv);
-      }
-    }
-  }
-
   // Phase-C ownership: a thread owns 8 consecutive dims (one 16B load
   // per token) — the ablation probe showed b32 V loads were 64% of the
   // kernel (8x more VMEM instructions per byte than phase A's b128s).
@@ -138,168 +150,50 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
 
-  // KPRE: raw K rows for the chunk about to be scored, loaded one full
-  // chunk ahead (16 b128 loads live across phases B+C of the previous
-  // chunk — the latency they need to hide).
-  constexpr bool USE_KPRE = KPRE && !MFMA_A && !KV8;
-  constexpr bool USE_KPRE8 = KPRE && !MFMA_A && KV8;
-  u16x8 kpre[USE_KPRE ? DHEAD / 8 : 1];
-  u8x16 kpre8[USE_KPRE8 ? DHEAD / 16 : 1];
+  // Raw K row for the chunk about to be scored, loaded one full chunk
+  // ahead: the 16B loads stay live across phases B+C of the previous
+  // chunk — the latency they need to hide. Without this the compiler
+  // sinks the loads into the consume loop and ~2 are in flight per wave
+  // (ISA audit, profiles/r02_decode_kpre.md).
+  kvec_t kpre[DHEAD / KVEC];
   auto issue_kpre = [&](int cbase) {
     const int tok = min(cbase + (int)threadIdx.x, p_end - 1);
     const int64_t roff =
         (((int64_t)btable[tok / block_size] * Hkv + hkv) *
              (int64_t)block_size + tok % block_size) * DHEAD;
-    if constexpr (USE_KPRE8) {
-      const uint8_t* krow = (const uint8_t*)k_cache + roff;
+    const elem_t* krow = (const elem_t*)k_cache + roff;
 #pragma unroll
-      for (int j = 0; j < DHEAD / 16; ++j)
-        kpre8[j] = *reinterpret_cast<const u8x16*>(krow + j * 16);
-    } else {
-      const uint16_t* krow = k_cache + roff;
-#pragma unroll
-      for (int j = 0; j < (USE_KPRE ? DHEAD / 8 : 1); ++j)
-        kpre[j] = *reinterpret_cast<const u16x8*>(krow + j * 8);
-    }
+    for (int j = 0; j < DHEAD / KVEC; ++j)
+      kpre[j] = *reinterpret_cast<const kvec_t*>(krow + j * KVEC);
   };
-  if constexpr (USE_KPRE || USE_KPRE8) issue_kpre(p_start);
+  issue_kpre(p_start);
 
   for (int base = p_start; base < p_end; base += CHUNK) {
     const int chunk_n = min(CHUNK, p_end - base);
 
     // --- Phase A: scores -------------------------------------------------
-    if constexpr (MFMA_A) {
-      // 16-token MFMA tiles; each wave owns alternating groups of 4.
-      const int ntiles = (chunk_n + 15) / 16;
-      const int l = threadIdx.x & (WAVE - 1);
-      const int l_lo = l & 15, l_hi = l >> 4;
-      for (int t0 = wid * 4; t0 < ntiles; t0 += nwaves * 4) {
-        const int nt = min(4, ntiles - t0);
-        u16x8 bfr[4][NKK];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (u >= nt) continue;
-          const int tok = min(base + (t0 + u) * 16 + l_lo, p_end - 1);
-          const int64_t blk = btable[tok / block_size];
-          const uint16_t* krow =
-              k_cache + (((blk * Hkv + hkv) * (int64_t)block_size +
-                          tok % block_size)) * DHEAD;
-#pragma unroll
-          for (int kk = 0; kk < NKK; ++kk)
-            bfr[u][kk] = *reinterpret_cast<const u16x8*>(
-                krow + kk * 32 + l_hi * 8);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (u >= nt) continue;
-          floatx4 sacc = floatx4{0, 0, 0, 0};
-#pragma unroll
-          for (int kk = 0; kk < NKK; ++kk)
-            sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                qfrag[kk], *reinterpret_cast<bf16x8*>(&bfr[u][kk]), sacc,
-                0, 0, 0);
-          // C[row=l_hi*4+r][col=l_lo]: row = query g, col = token
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int g = l_hi * 4 + r;
-            const int ci = (t0 + u) * 16 + l_lo;
-            if (g < G && ci < chunk_n) s_lds[g][ci] = sacc[r];
-          }
-        }
-      }
-    } else if constexpr (USE_KPRE) {
-      if ((int)threadIdx.x < chunk_n) {
-        float s[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) s[g] = 0.f;
-#pragma unroll
-        for (int j = 0; j < DHEAD / 8; ++j) {
-          float kv[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) kv[i] = bf16_to_f32(kpre[j][i]);
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-              s[g] += q_lds[g][j * 8 + i] * kv[i];
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) s_lds[g][threadIdx.x] = s[g];
-      }
-      // scores consumed: issue the NEXT chunk's K rows now so they
-      // fly during softmax + V accumulation
-      if (base + CHUNK < p_end) issue_kpre(base + CHUNK);
-    } else if constexpr (USE_KPRE8) {
-      if ((int)threadIdx.x < chunk_n) {
-        float s[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) s[g] = 0.f;
-#pragma unroll
-        for (int j = 0; j < DHEAD / 16; ++j) {
-          float kv[16];
-#pragma unroll
-          for (int i = 0; i < 16; ++i) kv[i] = fp8_to_f32(kpre8[j][i]);
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              s[g] += q_lds[g][j * 16 + i] * kv[i];
-          }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) s_lds[g][threadIdx.x] = s[g];
-      }
-      if (base + CHUNK < p_end) issue_kpre(base + CHUNK);
-    } else if ((int)threadIdx.x < chunk_n) {
-      const int tok = base + threadIdx.x;
-      const int64_t blk = btable[tok / block_size];
-      const int64_t roff =
-          (((blk * Hkv + hkv) * (int64_t)block_size + tok % block_size)) *
-          DHEAD;
+    if ((int)threadIdx.x < chunk_n) {
       float s[G];
 #pragma unroll
       for (int g = 0; g < G; ++g) s[g] = 0.f;
-      if constexpr (KV8) {
-        const uint8_t* krow = (const uint8_t*)k_cache + roff;
-        u8x16 kraw[DHEAD / 16];
 #pragma unroll
-        for (int j = 0; j < DHEAD / 16; ++j)
-          kraw[j] = *reinterpret_cast<const u8x16*>(krow + j * 16);
+      for (int j = 0; j < DHEAD / KVEC; ++j) {
+        float kv[KVEC];
 #pragma unroll
-        for (int j = 0; j < DHEAD / 16; ++j) {
-          float kv[16];
+        for (int i = 0; i < KVEC; ++i) kv[i] = CE::to_f32(kpre[j][i]);
 #pragma unroll
-          for (int i = 0; i < 16; ++i) kv[i] = fp8_to_f32(kraw[j][i]);
+        for (int g = 0; g < G; ++g) {
 #pragma unroll
-          for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              s[g] += q_lds[g][j * 16 + i] * kv[i];
-          }
-        }
-      } else {
-        const uint16_t* krow = k_cache + roff;
-        u16x8 kraw[DHEAD / 8];
-#pragma unroll
-        for (int j = 0; j < DHEAD / 8; ++j)
-          kraw[j] = *reinterpret_cast<const u16x8*>(krow + j * 8);
-#pragma unroll
-        for (int j = 0; j < DHEAD / 8; ++j) {
-          float kv[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) kv[i] = bf16_to_f32(kraw[j][i]);
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-              s[g] += q_lds[g][j * 8 + i] * kv[i];
-          }
+          for (int i = 0; i < KVEC; ++i)
+            s[g] += q_lds[g][j * KVEC + i] * kv[i];
         }
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) s_lds[g][threadIdx.x] = s[g];
     }
+    // scores consumed: issue the NEXT chunk's K rows now so they fly
+    // during softmax + V accumulation
+    if (base + CHUNK < p_end) issue_kpre(base + CHUNK);
     __syncthreads();
 
     // --- Phase B: online softmax per head --------------------------------
@@ -326,7 +220,10 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
     }
     __syncthreads();
 
-    // --- Phase C: V accumulation (16B lane loads, 4-pass batches) --------
+    // --- Phase C: V accumulation (VPS-token load batches) ----------------
+    // The multiply-accumulate is written out three times on purpose:
+    // behind a shared helper the compiler schedules 12 of the 24 kernels
+    // differently (profiles/r03_decode_prune.md).
     {
 #pragma unroll
       for (int g = 0; g < G; ++g)
@@ -339,16 +236,10 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
                  tok % block_size)) * DHEAD + d8;
       };
       auto load_v = [&](int64_t off, float v[8]) {
-        if constexpr (KV8) {
-          const u8x8 raw = *reinterpret_cast<const u8x8*>(
-              (const uint8_t*)v_cache + off);
+        const vvec_t raw =
+            *reinterpret_cast<const vvec_t*>((const elem_t*)v_cache + off);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = fp8_to_f32(raw[i]);
-        } else {
-          const u16x8 raw = *reinterpret_cast<const u16x8*>(v_cache + off);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = bf16_to_f32(raw[i]);
-        }
+        for (int i = 0; i < 8; ++i) v[i] = CE::to_f32(raw[i]);
       };
       int ps = 0;
       if constexpr (!KV8) {
@@ -376,16 +267,17 @@ __global__ __launch_bounds__(NTHREADS, (OCC > 0 ? OCC : (G <= 2 ? 4 : 3))) void 
           }
         }
       } else {
-        for (; ps + 4 <= npass; ps += 4) {
-          int64_t voff[4];
+        // fp8 rows are half as wide: batches are converted as they land
+        for (; ps + VPS <= npass; ps += VPS) {
+          int64_t voff[VPS];
 #pragma unroll
-          for (int u = 0; u < 4; ++u)
+          for (int u = 0; u < VPS; ++u)
             voff[u] = vrow_off(base + (ps + u) * C_PAR + cpar);
-          float v4[4][8];
+          float v4[VPS][8];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) load_v(voff[u], v4[u]);
+          for (int u = 0; u < VPS; ++u) load_v(voff[u], v4[u]);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
+          for (int u = 0; u < VPS; ++u) {
             const int tok_i = (ps + u) * C_PAR + cpar;
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -469,7 +361,7 @@ __global__ __launch_bounds__(128) void paged_attn_reduce_kernel(
       min(max_parts, (seq_lens[seq] + partition_size - 1) / partition_size);
   const float* ml = tmp_ml + ((int64_t)seq * Hq + hq) * max_parts * 2;
 
-  __shared__ float w[512];
+  __shared__ float w[MAX_PARTS];
   __shared__ float l_sh;
   if (threadIdx.x == 0) {
     float M = -INFINITY;
@@ -495,36 +387,6 @@ __global__ __launch_bounds__(128) void paged_attn_reduce_kernel(
   }
 }
 
-static bool use_mfma_a() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("HELIX_DECODE_MFMA");
-    v = (e != nullptr && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-// A/B knobs for the round-2 decode pipeline (defaults = measured best)
-static int decode_vps() {
-  static int v = -1;
-  if (v < 0) v = env_int("HELIX_DECODE_VPS", 4);
-  return v;
-}
-static int decode_occ() {
-  static int v = -1;
-  if (v < 0) v = env_int("HELIX_DECODE_OCC", 0);
-  return v;
-}
-static int decode_kpre() {
-  static int v = -1;
-  if (v < 0) v = env_int("HELIX_DECODE_KPRE", 1);
-  return v;
-}
-
 template <int DHEAD, int G>
 void launch_decode(uint16_t* out, float* tmp_out, float* tmp_ml,
                    const uint16_t* q, const uint16_t* kc, const uint16_t* vc,
@@ -532,51 +394,32 @@ void launch_decode(uint16_t* out, float* tmp_out, float* tmp_ml,
                    int Hkv, int block_size, int max_blocks, int eff_part,
                    int nparts, int max_parts, int window, bool kv8,
                    hipStream_t stream) {
-#define LAUNCH_PD(MF, K8, VPS, OCC, KP)                                      \
-  hipLaunchKernelGGL(                                                        \
-      (paged_attn_decode_kernel<DHEAD, G, MF, K8, VPS, OCC, KP>),            \
-      dim3(B, Hkv, nparts), dim3(NTHREADS), 0, stream, out,                  \
-      tmp_out, tmp_ml, q, kc, vc, bt, lens, scale, Hkv,                      \
-      block_size, max_blocks, eff_part, max_parts, window)
-  if (kv8) {
-    if (decode_kpre()) LAUNCH_PD(false, true, 4, 2, true);
-    else               LAUNCH_PD(false, true, 4, 0, false);
-  } else if (use_mfma_a()) {
-    LAUNCH_PD(true, false, 4, 0, false);
-  } else {
-    const int vps = decode_vps(), occ = decode_occ();
-    if (decode_kpre()) {
-      // measured defaults (profiles/r02_decode_kpre.md): K-prefetch +
-      // waves/EU floor 2 everywhere (+5.4% e2e at B=512). When the
-      // grid underfills the chip (< 2048 workgroups on 256 CUs x 4
-      // SIMDs), per-wave pipelining has to replace occupancy-based
-      // latency hiding: the 8-deep V staging wins those shapes
-      // (4.25-4.29 vs 3.6-3.7 TB/s at B<=64 / L>=2048) but loses the
-      // full-grid B=512 headline (27.5k vs 28.1k tok/s), so it is
-      // grid-gated, not global. HELIX_DECODE_VPS / _OCC override.
-      const bool vps_forced = getenv("HELIX_DECODE_VPS") != nullptr;
-      const bool small_grid = B * Hkv * nparts < 2048;
-      const bool deep = vps_forced ? (vps >= 8) : small_grid;
-      if (deep)                      LAUNCH_PD(false, false, 8, 2, true);
-      else if (occ == 0 || occ == 2) LAUNCH_PD(false, false, 4, 2, true);
-      else                           LAUNCH_PD(false, false, 4, 0, true);
-    }
-    else if (occ == 2)        LAUNCH_PD(false, false, 4, 2, false);
-    else if (vps >= 8 && occ >= 4) LAUNCH_PD(false, false, 8, 4, false);
-    else if (vps >= 8)        LAUNCH_PD(false, false, 8, 0, false);
-    else if (occ >= 4)        LAUNCH_PD(false, false, 4, 4, false);
-    else                      LAUNCH_PD(false, false, 4, 0, false);
-  }
+#define LAUNCH_PD(K8, VPS)                                                   \
+  hipLaunchKernelGGL((paged_attn_decode_kernel<DHEAD, G, K8, VPS>),          \
+                     dim3(B, Hkv, nparts), dim3(NTHREADS), 0, stream, out,   \
+                     tmp_out, tmp_ml, q, kc, vc, bt, lens, scale, Hkv,       \
+                     block_size, max_blocks, eff_part, max_parts, window)
+  // Measured in profiles/r02_decode_kpre.md. A grid under 2048
+  // workgroups underfills the chip (256 CUs x 4 SIMDs), so
+  // per-wave depth has to replace occupancy-based latency hiding: the
+  // 8-deep V staging wins those shapes (4.25-4.29 vs 3.6-3.7 TB/s at
+  // B<=64 / L>=2048) but loses the full-grid B=512 headline (27.5k vs
+  // 28.1k tok/s).
+  if (kv8)                          LAUNCH_PD(true, 4);
+  else if (B * Hkv * nparts < 2048) LAUNCH_PD(false, 8);
+  else                              LAUNCH_PD(false, 4);
 #undef LAUNCH_PD
 }
 
 }  // namespace
 
+int64_t decode_part_quant() { return PART_QUANT; }
+
 void paged_attn_decode(torch::Tensor out, torch::Tensor q,
                        torch::Tensor k_cache, torch::Tensor v_cache,
                        torch::Tensor block_tables, torch::Tensor seq_lens,
                        double scale, torch::Tensor tmp_out,
-                       torch::Tensor tmp_ml, int64_t max_len_hint,
+                       torch::Tensor tmp_ml, int64_t max_len,
                        int64_t window) {
   const int B = q.size(0);
   const int Hq = q.size(1);
@@ -584,27 +427,45 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
   const int Hkv = k_cache.size(1);
   const int block_size = k_cache.size(2);
   const int max_blocks = block_tables.size(1);
-  const int max_parts = tmp_out.size(2);
-  const int G = Hq / Hkv;
+  const int max_parts = tmp_out.dim() == 4 ? tmp_out.size(2) : 0;
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
-  TORCH_CHECK(G <= MAX_G && Hq % Hkv == 0);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be a multiple of Hkv");
+  const int G = Hq / Hkv;
   TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "G must be 1/2/4/8");
-  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32);
+  TORCH_CHECK(max_len >= 1, "max_len must be >= 1, got ", max_len);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  out.scalar_type() == torch::kBFloat16,
+              "q and out must be bf16");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(),
+              "k_cache and v_cache must share a dtype");
+  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32,
+              "block_tables must be int32");
+  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32,
+              "seq_lens must be int32");
+  TORCH_CHECK(seq_lens.size(0) == B && block_tables.size(0) == B,
+              "seq_lens and block_tables must have B = ", B, " rows");
+  TORCH_CHECK(q.is_contiguous() && out.is_contiguous() &&
+                  k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                  block_tables.is_contiguous() && seq_lens.is_contiguous() &&
+                  tmp_out.is_contiguous() && tmp_ml.is_contiguous(),
+              "paged_attn_decode takes contiguous tensors");
+  TORCH_CHECK(tmp_out.scalar_type() == torch::kFloat32 && max_parts >= 1 &&
+                  tmp_out.sizes() == at::IntArrayRef({B, Hq, max_parts, D}),
+              "tmp_out must be fp32 [B, Hq, max_parts, D] with B = ", B,
+              ", Hq = ", Hq, ", D = ", D, "; got ", tmp_out.sizes());
+  TORCH_CHECK(tmp_ml.scalar_type() == torch::kFloat32 &&
+                  tmp_ml.sizes() == at::IntArrayRef({B, Hq, max_parts, 2}),
+              "tmp_ml must be fp32 [B, Hq, max_parts, 2] with tmp_out's "
+              "max_parts = ", max_parts, "; got ", tmp_ml.sizes());
 
-  const int max_len = (int)max_len_hint;
-  const int max_useful = cdiv(max_len, PART_QUANT);
-  // split-K sizing target: enough workgroups to fill 256 CUs. 1024 was
-  // round-1's tuning; HELIX_DECODE_TARGET_WGS re-tunes it for the
-  // round-2 pipeline on underfilled (small-B, long-L) shapes.
-  static int target_wgs = [] {
-    const char* e = getenv("HELIX_DECODE_TARGET_WGS");
-    return e ? atoi(e) : 1024;
-  }();
-  int nparts = std::max(1, target_wgs / std::max(1, B * Hkv));
-  nparts = std::min({nparts, max_useful, max_parts});
-  int eff_part = cdiv(cdiv(max_len, nparts), PART_QUANT) * PART_QUANT;
-  nparts = cdiv(max_len, eff_part);
+  // split-K sizing: enough workgroups to fill the 256 CUs, never more
+  // partitions than the longest row needs, the workspace holds or the
+  // reduce kernel's weight array takes
+  const int max_useful = cdiv((int)max_len, PART_QUANT);
+  int nparts = std::max(1, TARGET_WGS / std::max(1, B * Hkv));
+  nparts = std::min({nparts, max_useful, max_parts, MAX_PARTS});
+  int eff_part = cdiv(cdiv((int)max_len, nparts), PART_QUANT) * PART_QUANT;
+  nparts = cdiv((int)max_len, eff_part);
 
   auto stream = at::hip::getCurrentHIPStream();
   auto* o = (uint16_t*)out.data_ptr();

@@ -139,6 +139,11 @@ def test_attn_prefill(hq, hkv, d, lens):
     (64, 8, 128, [90, 1024]),
     (12, 12, 64, [50]),
     (32, 8, 128, [2048]),   # exercises split-K partitions
+    # G=2; split-K into 6 partitions with a 60-token last one; the short
+    # row leaves dead partitions
+    (16, 8, 128, [129, 700]),
+    (8, 2, 64, [129, 700]),     # G=4 at D=64
+    (16, 2, 64, [300]),         # G=8 at D=64
 ])
 def test_paged_attn_decode(hq, hkv, d, lens):
     torch.manual_seed(8)
@@ -157,6 +162,86 @@ def test_paged_attn_decode(hq, hkv, d, lens):
         bt[b, :n] = torch.arange(nxt, nxt + n, dtype=torch.int32)
         nxt += n
     seq_lens = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    scale = d ** -0.5
+    got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale)
+    want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
+                                 seq_lens.cpu(), scale)
+    assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+
+
+def _paged_case(lens, hq, hkv, d, bs=16):
+    """Random q and bf16 paged caches with each row's blocks laid out
+    back to back from block 1."""
+    B = len(lens)
+    nblk = [(l + bs - 1) // bs for l in lens]
+    q = torch.randn(B, hq, d, dtype=torch.bfloat16, device=DEV)
+    kc = torch.randn(sum(nblk) + 1, hkv, bs, d, dtype=torch.bfloat16,
+                     device=DEV)
+    vc = torch.randn_like(kc)
+    bt = torch.zeros(B, max(nblk), dtype=torch.int32)
+    nxt = 1
+    for b, n in enumerate(nblk):
+        bt[b, :n] = torch.arange(nxt, nxt + n, dtype=torch.int32)
+        nxt += n
+    seq_lens = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    return q, kc, vc, bt.to(DEV), seq_lens
+
+
+def test_paged_attn_decode_full_grid():
+    """The kernel the B=512 headline runs. B*Hkv = 2048 leaves nparts = 1,
+    so the grid is 2048 workgroups and the host picks the VPS=4 variant
+    (every smaller case in this file gets VPS=8). G=2. Lengths: a
+    one-token row, an exactly full chunk, and second chunks of 1 and 44
+    tokens (the chunk-2 K prefetch issues; the batch-of-4 V loop has a
+    tail)."""
+    torch.manual_seed(16)
+    hq, hkv, d = 16, 8, 128
+    lens = [[1, 127, 128, 129, 300][i % 5] for i in range(256)]
+    q, kc, vc, bt, seq_lens = _paged_case(lens, hq, hkv, d)
+    scale = d ** -0.5
+    got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale)
+    want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
+                                 seq_lens.cpu(), scale)
+    assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+
+
+def test_decode_partition_constant():
+    """The Python workspace sizing and the kernel's split-K quantum are
+    one number."""
+    assert ops.DECODE_PARTITION == ops._native().DECODE_PART_QUANT
+
+
+def test_paged_attn_decode_rejects_bad_args():
+    """Host checks fire before any launch: a zero max_len (it used to
+    divide by zero) and a workspace sized for a smaller batch."""
+    torch.manual_seed(17)
+    hq, hkv, d = 8, 8, 128
+    q, kc, vc, bt, seq_lens = _paged_case([40, 40], hq, hkv, d)
+    scale = d ** -0.5
+    with pytest.raises(RuntimeError, match="max_len"):
+        ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale, max_len=0)
+    ws1 = ops.decode_workspace(1, hq, d, 40, DEV)
+    with pytest.raises(RuntimeError, match="tmp_out"):
+        ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale, workspace=ws1,
+                              max_len=40)
+    torch.cuda.synchronize()
+    # the same arguments with a matching workspace are accepted
+    ws2 = ops.decode_workspace(2, hq, d, 40, DEV)
+    got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale,
+                                workspace=ws2, max_len=40)
+    want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
+                                 seq_lens.cpu(), scale)
+    assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+
+
+def test_paged_attn_decode_partition_cap():
+    """One kv head at batch 1 with a 65 600-token context: split-K sizing
+    asks for 1024 partitions and the workspace allows 513; the cap of 512
+    (the reduce kernel's weight array) makes it 257 partitions of 256
+    tokens."""
+    torch.manual_seed(18)
+    d = 128
+    q, kc, vc, bt, seq_lens = _paged_case([65600], 1, 1, d)
     scale = d ** -0.5
     got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale)
     want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
@@ -383,11 +468,17 @@ def test_gemm_fp8_bias_gelu():
                                rtol=0.08)
 
 
-def test_fp8_kv_decode_gpu():
+@pytest.mark.parametrize("d,lens,window", [
+    (128, [77] * 4, 0),         # one partial chunk
+    (128, [129, 1100], 0),      # next-chunk K prefetch; split-K, 9 parts
+    (64, [129, 700], 0),        # D=64
+    (128, [700], 256),          # sliding window over split-K
+])
+def test_fp8_kv_decode_gpu(d, lens, window):
     """Decode kernel over an fp8 (e4m3) cache matches the dequantized
     reference, and the HW cvt encodings match torch float8_e4m3fn."""
     torch.manual_seed(0)
-    B, hq, hkv, d, bs, L = 4, 8, 2, 128, 16, 77
+    B, hq, hkv, bs, L = len(lens), 8, 2, 16, max(lens)
     nb = (L + bs - 1) // bs
     k = torch.randn(L, hkv, d, dtype=torch.bfloat16, device="cuda")
     v = torch.randn(L, hkv, d, dtype=torch.bfloat16, device="cuda")
@@ -397,18 +488,19 @@ def test_fp8_kv_decode_gpu():
     vc = torch.zeros_like(kc)
     bt = (torch.arange(B * nb, dtype=torch.int32, device="cuda")
           .reshape(B, nb) + 1)
-    lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    lens = torch.tensor(lens, dtype=torch.int32, device="cuda")
     for b in range(B):
-        slots = (torch.arange(L, dtype=torch.int64, device="cuda")
+        n = int(lens[b])
+        slots = (torch.arange(n, dtype=torch.int64, device="cuda")
                  + (1 + b * nb) * bs)
-        ops.reshape_and_cache(ops.kv_fp8_quant(k), ops.kv_fp8_quant(v),
-                              kc, vc, slots)
+        ops.reshape_and_cache(ops.kv_fp8_quant(k[:n]),
+                              ops.kv_fp8_quant(v[:n]), kc, vc, slots)
     scale = d ** -0.5
-    out = ops.paged_attn_decode(q, kc, vc, bt, lens, scale)
+    out = ops.paged_attn_decode(q, kc, vc, bt, lens, scale, window=window)
     # fp32 torch reference on the dequantized cache (CPU)
     want = ops.paged_attn_decode(q.cpu(), ops.kv_fp8_dequant(kc).cpu(),
                                  ops.kv_fp8_dequant(vc).cpu(), bt.cpu(),
-                                 lens.cpu(), scale)
+                                 lens.cpu(), scale, window=window)
     torch.testing.assert_close(out.cpu().float(), want.float(), atol=3e-2,
                                rtol=3e-2)
 
