@@ -139,6 +139,8 @@ def apply(file: str = typer.Option(..., "-f", "--file"),
 def chat(message: str = typer.Argument(...),
          model: str = typer.Option("", "--model"),
          app_id: str = typer.Option("", "--app"),
+         lora_id: str = typer.Option("", "--lora-id",
+                                     help="LoRA adapter id on the model"),
          url: str = typer.Option("", "--url"),
          stream: bool = typer.Option(True)):
     """One-shot chat against /v1/chat/completions."""
@@ -150,6 +152,8 @@ def chat(message: str = typer.Argument(...),
         body["model"] = model
     if app_id:
         body["app_id"] = app_id
+    if lora_id:
+        body["lora_id"] = lora_id
     with httpx.Client(timeout=300) as http:
         if stream:
             with http.stream("POST", f"{api}/v1/chat/completions",

@@ -87,18 +87,24 @@ class HelixClient:
 
     # -- chat / sessions (client/session.go) ---------------------------------
     def chat(self, messages: List[dict], model: str = "",
-             app_id: str = "", stream: bool = False, **kw) -> dict:
+             app_id: str = "", stream: bool = False,
+             lora_id: str = "", **kw) -> dict:
         body = {"messages": messages, "stream": False, **kw}
         if model:
             body["model"] = model
+        if lora_id:
+            body["lora_id"] = lora_id
         params = {"app_id": app_id} if app_id else None
         return self._post("/v1/chat/completions", body, params=params)
 
     def chat_stream(self, messages: List[dict], model: str = "",
-                    app_id: str = "", **kw) -> Iterator[dict]:
+                    app_id: str = "", lora_id: str = "",
+                    **kw) -> Iterator[dict]:
         body = {"messages": messages, "stream": True, **kw}
         if model:
             body["model"] = model
+        if lora_id:
+            body["lora_id"] = lora_id
         params = {"app_id": app_id} if app_id else {}
         with self._http.stream(
                 "POST", self.url + "/v1/chat/completions",

@@ -52,6 +52,7 @@ class Sequence:
     json_mask: object = None     # JSONByteMask when params.json_mode
     # streaming callback: fn(seq, new_token_id, finished)
     on_token: Optional[Callable] = None
+    lora: Optional[str] = None             # adapter name (None = base model)
 
     @property
     def total_len(self) -> int:
@@ -73,6 +74,8 @@ class EngineConfig:
     enable_prefix_caching: bool = True
     quantization: Optional[str] = None        # None | "fp8" (e4m3 W8A8)
     kv_cache_dtype: str = "bf16"              # "bf16" | "fp8" (e4m3 KV)
+    max_loras: int = 0                        # adapter slots (0 = LoRA off)
+    max_lora_rank: int = 16
 
 
 class LLMEngine:
@@ -95,6 +98,16 @@ class LLMEngine:
             from helix_amd.models.quant import quantize_model_fp8
             quantize_model_fp8(model)
         self.model = model
+        # per-request LoRA adapters: device-resident slot stacks hooked
+        # into the attention / MLP projections (models/lora.py)
+        self.lora = None
+        if cfg.max_loras > 0:
+            if tp_size > 1:
+                raise ValueError(
+                    "max_loras > 0 is not supported with tp_size > 1 "
+                    "(tensor-parallel-sharded adapters are not implemented)")
+            from helix_amd.models.lora import LoRAManager
+            self.lora = LoRAManager(model, cfg.max_loras, cfg.max_lora_rank)
 
         nkv = self.model_cfg.num_kv_heads // tp_size
         num_blocks = cfg.kv_cache_blocks
@@ -149,13 +162,14 @@ class LLMEngine:
         self._slots_np = np.zeros(cfg.max_num_seqs, dtype=np.int64)
         self._lens_np = np.zeros(cfg.max_num_seqs, dtype=np.int32)
         self._rows_np = np.zeros(cfg.max_num_seqs, dtype=np.intp)
+        self._lora_np = np.full(cfg.max_num_seqs, -1, dtype=np.int32)
         self.graph_runner = None
         if self.device.type == "cuda" and not cfg.enforce_eager:
             from helix_amd.engine.graph_runner import CUDAGraphRunner
             self.graph_runner = CUDAGraphRunner(
                 self.model, self.kv.caches, self.decode_ws,
                 cfg.max_model_len, cfg.block_size, cfg.max_num_seqs,
-                self.device)
+                self.device, lora=self.lora is not None)
 
     # ------------------------------------------------------------------
     def _auto_kv_blocks(self, nkv: int) -> int:
@@ -176,16 +190,73 @@ class LLMEngine:
     # ------------------------------------------------------------------
     def add_request(self, seq_id: str, prompt_ids: List[int],
                     params: SamplingParams,
-                    on_token: Optional[Callable] = None) -> Sequence:
+                    on_token: Optional[Callable] = None,
+                    lora: Optional[str] = None) -> Sequence:
         if len(prompt_ids) >= self.cfg.max_model_len:
             raise ValueError(
                 f"prompt length {len(prompt_ids)} >= max_model_len "
                 f"{self.cfg.max_model_len}")
+        if lora is not None:
+            if self.lora is None:
+                raise ValueError(
+                    f"LoRA adapter {lora!r} requested but the engine was "
+                    "built with max_loras=0")
+            if lora not in self.lora.adapters:
+                raise ValueError(f"unknown LoRA adapter {lora!r}")
         seq = Sequence(seq_id=seq_id, prompt_ids=list(prompt_ids),
-                       params=params, on_token=on_token)
+                       params=params, on_token=on_token, lora=lora)
         self.seqs[seq_id] = seq
         self.waiting.append(seq)
         return seq
+
+    # -- LoRA adapters --------------------------------------------------
+    def _lora_in_use(self, name: str) -> bool:
+        return any(s.lora == name for s in self.waiting + self.running)
+
+    def add_lora(self, name: str, path: str):
+        """Register (or reload) the HF-PEFT adapter at `path` as `name`.
+        It is copied into a device slot lazily, when a request needs it."""
+        if self.lora is None:
+            raise ValueError("engine was built with max_loras=0")
+        if self._lora_in_use(name):
+            raise ValueError(
+                f"LoRA adapter {name!r} is referenced by queued or running "
+                "sequences; cannot reload it")
+        self.lora.add(name, path)
+
+    def remove_lora(self, name: str):
+        if self.lora is None or name not in self.lora.adapters:
+            raise ValueError(f"unknown LoRA adapter {name!r}")
+        if self._lora_in_use(name):
+            raise ValueError(
+                f"LoRA adapter {name!r} is referenced by queued or running "
+                "sequences; cannot remove it")
+        self.lora.remove(name)
+
+    def list_loras(self) -> List[str]:
+        return self.lora.names() if self.lora is not None else []
+
+    def _pinned_loras(self, batch: List[Sequence]) -> set:
+        """Adapters whose slot must stay: used by a RUNNING sequence, by a
+        WAITING one that holds blocks (mid-chunked-prefill), or by one
+        admitted earlier in this step."""
+        pinned = {s.lora for s in self.running if s.lora}
+        pinned.update(s.lora for s in batch if s.lora)
+        pinned.update(s.lora for s in self.waiting
+                      if s.lora and s.block_table)
+        return pinned
+
+    def _lora_slots(self, lora_names) -> Optional[List[int]]:
+        """Slot per name, or None when no row uses an adapter."""
+        if self.lora is None or not any(lora_names):
+            return None
+        out = []
+        for n in lora_names:
+            s = self.lora.slot_of(n)
+            if n is not None and s < 0:
+                raise RuntimeError(f"LoRA adapter {n!r} is not resident")
+            out.append(s)
+        return out
 
     def cancel(self, seq_id: str):
         seq = self.seqs.get(seq_id)
@@ -248,12 +319,18 @@ class LLMEngine:
             seq = self.waiting[0]
             L = len(seq.prompt_ids)
             first = not seq.block_table
+            if seq.lora is not None and self.lora.acquire(
+                    seq.lora, self._pinned_loras(batch)) < 0:
+                break                  # every slot pinned: wait (FIFO)
             matched: List[int] = []
             if first:
                 # prefix-cache match (chain hashes over full blocks)
                 if self.cfg.enable_prefix_caching:
                     if not seq.block_hashes:
-                        h = b""
+                        # K/V depend on the adapter (and its load
+                        # generation): seed the chain with it
+                        h = b"" if seq.lora is None \
+                            else self.lora.hash_seed(seq.lora)
                         for i in range(L // bs):
                             h = chain_hash(h,
                                            seq.prompt_ids[i * bs:(i + 1) * bs])
@@ -321,6 +398,8 @@ class LLMEngine:
         bs = self.cfg.block_size
         input_ids, positions, slots, cu_q, cu_k = [], [], [], [0], [0]
         gather_blk, gather_off = [], []
+        row_slots = self._lora_slots([s.lora for s in batch])
+        tok_slots: List[int] = []
         targets = getattr(self, "_chunk_target", {})
         any_cached = any(s.cached_prefix for s in batch)
         for seq in batch:
@@ -331,6 +410,8 @@ class LLMEngine:
             slots.extend(self._slot(seq, p) for p in range(P, L))
             cu_q.append(cu_q[-1] + L - P)
             cu_k.append(cu_k[-1] + L)
+            if row_slots is not None:
+                tok_slots.extend([row_slots[len(cu_q) - 2]] * (L - P))
             if any_cached:
                 for p in range(L):
                     gather_blk.append(seq.block_table[p // bs])
@@ -347,7 +428,10 @@ class LLMEngine:
             gather_blk=(torch.tensor(gather_blk, dtype=torch.int64,
                                      device=dev) if any_cached else None),
             gather_off=(torch.tensor(gather_off, dtype=torch.int64,
-                                     device=dev) if any_cached else None))
+                                     device=dev) if any_cached else None),
+            lora_slots=(torch.tensor(tok_slots, dtype=torch.int32,
+                                     device=dev)
+                        if row_slots is not None else None))
         ids = torch.tensor(input_ids, dtype=torch.int64, device=dev)
         hidden = self.model(ids, self.kv.caches, meta)
         # register this batch's newly COMPLETED full blocks in the
@@ -439,6 +523,12 @@ class LLMEngine:
             slots_np[nb_] = self._slot(seq, pos)
             lens_np[nb_] = pos + 1
             rows_np[nb_] = seq.row
+            if self.lora is not None:
+                ls = self.lora.slot_of(seq.lora)
+                if ls < 0 and seq.lora is not None:
+                    raise RuntimeError(
+                        f"LoRA adapter {seq.lora!r} is not resident")
+                self._lora_np[nb_] = ls
             nb_ += 1
         if not batch:
             return []
@@ -450,15 +540,22 @@ class LLMEngine:
         if self.graph_runner is not None:
             logits = self.graph_runner.run(ids_np[:B], pos_np[:B],
                                            slots_np[:B], bt_np,
-                                           lens_np[:B], max_len)
+                                           lens_np[:B], max_len,
+                                           lora_slots=(self._lora_np[:B]
+                                                       if self.lora is not None
+                                                       else None))
         else:
+            row_slots = self._lora_slots([s.lora for s in batch])
             meta = DecodeMeta(
                 block_tables=torch.from_numpy(bt_np).to(dev),
                 seq_lens=torch.from_numpy(lens_np[:B].copy()).to(dev),
                 slot_mapping=torch.from_numpy(slots_np[:B].copy()).to(dev),
                 positions=torch.from_numpy(pos_np[:B].copy()).to(dev),
                 max_len=max_len,
-                workspace=self.decode_ws)
+                workspace=self.decode_ws,
+                lora_slots=(torch.tensor(row_slots, dtype=torch.int32,
+                                         device=dev)
+                            if row_slots is not None else None))
             ids = torch.from_numpy(ids_np[:B].copy()).to(dev)
             hidden = self.model(ids, self.kv.caches, meta)
             logits = self.model.compute_logits(hidden)
@@ -759,7 +856,9 @@ class LLMEngine:
 
     # ------------------------------------------------------------------
     def generate(self, prompts: List[List[int]],
-                 params: SamplingParams) -> List[List[int]]:
+                 params: SamplingParams,
+                 loras: Optional[List[Optional[str]]] = None
+                 ) -> List[List[int]]:
         """Synchronous batch generate (used by tests and bench)."""
         # ids must be identical across SPMD TP ranks: the seedless
         # sampling fallback seeds from crc32(seq_id), so an id built
@@ -767,8 +866,12 @@ class LLMEngine:
         self._gen_calls = getattr(self, "_gen_calls", 0) + 1
         ids = [f"gen-{self._gen_calls}-{i}"
                for i in range(len(prompts))]
-        for sid, p in zip(ids, prompts):
-            self.add_request(sid, p, params)
+        if loras is None:
+            loras = [None] * len(prompts)
+        if len(loras) != len(prompts):
+            raise ValueError("loras must have one entry per prompt")
+        for sid, p, lo in zip(ids, prompts, loras):
+            self.add_request(sid, p, params, lora=lo)
         while self.has_work:
             self.step()
         return [self.seqs[sid].output_ids for sid in ids]

@@ -19,7 +19,8 @@ MIN_LEN_BUCKET = 512
 
 class CUDAGraphRunner:
     def __init__(self, model, kv_caches, workspace, max_model_len: int,
-                 block_size: int, max_batch: int, device):
+                 block_size: int, max_batch: int, device,
+                 lora: bool = False):
         self.model = model
         self.kv_caches = kv_caches
         self.workspace = workspace
@@ -45,6 +46,14 @@ class CUDAGraphRunner:
         self.h_lens = torch.ones(B, dtype=torch.int32, pin_memory=True)
         self.h_bt = torch.zeros(B, self.max_blocks, dtype=torch.int32,
                                 pin_memory=True)
+        # per-row LoRA adapter slots (only when the engine has a manager):
+        # pad rows are -1 = no adapter
+        self.in_lora = self.h_lora = None
+        if lora:
+            self.in_lora = torch.full((B,), -1, dtype=torch.int32,
+                                      device=device)
+            self.h_lora = torch.full((B,), -1, dtype=torch.int32,
+                                     pin_memory=True)
 
     def batch_bucket(self, n: int) -> int:
         for b in BATCH_BUCKETS:
@@ -66,7 +75,9 @@ class CUDAGraphRunner:
             slot_mapping=self.in_slots[:nb],
             positions=self.in_pos[:nb],
             max_len=lb,
-            workspace=self.workspace)
+            workspace=self.workspace,
+            lora_slots=(self.in_lora[:nb] if self.in_lora is not None
+                        else None))
         ids = self.in_ids[:nb]
         # Warm up on a side stream (allocator state, lazy inits).
         s = torch.cuda.Stream()
@@ -89,7 +100,7 @@ class CUDAGraphRunner:
         return {"graph": g, "logits": logits}
 
     def run(self, input_ids, positions, slots, block_tables, seq_lens,
-            max_len: int) -> torch.Tensor:
+            max_len: int, lora_slots=None) -> torch.Tensor:
         """All args numpy arrays (or lists); returns logits[:B]."""
         B = len(input_ids)
         nb = self.batch_bucket(B)
@@ -115,6 +126,12 @@ class CUDAGraphRunner:
         self.in_slots[:nb].copy_(self.h_slots[:nb], non_blocking=True)
         self.in_lens[:nb].copy_(self.h_lens[:nb], non_blocking=True)
         self.in_bt[:nb].copy_(self.h_bt[:nb], non_blocking=True)
+        if self.in_lora is not None:
+            self.h_lora[:nb] = -1
+            if lora_slots is not None:
+                self.h_lora[:B] = torch.as_tensor(lora_slots,
+                                                  dtype=torch.int32)
+            self.in_lora[:nb].copy_(self.h_lora[:nb], non_blocking=True)
 
         if key not in self.graphs:
             self.graphs[key] = self._capture(nb, lb)
@@ -145,6 +162,8 @@ class CUDAGraphRunner:
         self.in_slots.fill_(-1)
         self.in_lens.fill_(1)
         self.in_bt.zero_()
+        if self.in_lora is not None:
+            self.in_lora.fill_(-1)
         for lb in len_buckets:
             lb = min(lb, self.max_model_len)
             for nb in BATCH_BUCKETS:

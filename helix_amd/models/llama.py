@@ -105,6 +105,7 @@ class PrefillMeta:
     gather_blk: Optional[torch.Tensor] = None     # [Tk] int64
     gather_off: Optional[torch.Tensor] = None     # [Tk] int64
     is_prefill: bool = True
+    lora_slots: Optional[torch.Tensor] = None     # [T] int32, -1 = none
 
 
 @dataclass
@@ -117,6 +118,7 @@ class DecodeMeta:
     max_len: int = 0               # host-side max(seq_lens) (avoids sync)
     workspace: Optional[tuple] = None
     is_prefill: bool = False
+    lora_slots: Optional[torch.Tensor] = None     # [B] int32, -1 = none
 
 
 class HLinear(nn.Linear):
@@ -126,6 +128,19 @@ class HLinear(nn.Linear):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ops.linear(x, self.weight, self.bias)
+
+
+def _lora(out: torch.Tensor, x: torch.Tensor, lora, proj: str, meta):
+    """Per-row adapter delta on a projection's output (models/lora.py).
+    A no-op unless the module has adapter stacks AND the step names
+    slots, so a model without a manager issues today's kernel sequence."""
+    slots = getattr(meta, "lora_slots", None)
+    if lora is None or slots is None:
+        return out
+    A, B, n_off = lora.stacks[proj]
+    if not out.is_contiguous():
+        out = out.contiguous()
+    return ops.lora_apply(out, x, A, B, slots, lora.scale, n_off)
 
 
 class Attention(nn.Module):
@@ -142,11 +157,12 @@ class Attention(nn.Module):
         q, kv, h = self.nh * self.hd, self.nkv * self.hd, cfg.hidden_size
         self.qkv_proj = HLinear(h, q + 2 * kv, bias=cfg.attention_bias)
         self.o_proj = HLinear(q, h, bias=False)
+        self.lora = None               # LayerLoRA, set by LoRAManager
 
     def forward(self, x: torch.Tensor, cos_sin: torch.Tensor, kv_cache,
                 meta) -> torch.Tensor:
         T = x.shape[0]
-        qkv = self.qkv_proj(x)
+        qkv = _lora(self.qkv_proj(x), x, self.lora, "qkv_proj", meta)
         # fused strided split + rope + paged-cache write (one kernel, no
         # .contiguous() copies); compact K/V emitted only when the
         # fresh-prefill attention path consumes them directly
@@ -181,7 +197,8 @@ class Attention(nn.Module):
                                       meta.workspace,
                                       meta.max_len or None,
                                       window=self.window)
-        out = self.o_proj(o.view(T, -1))
+        o = o.view(T, -1)
+        out = _lora(self.o_proj(o), o, self.lora, "o_proj", meta)
         if self.tp_size > 1:
             from helix_amd import parallel
             out = parallel.tp_all_reduce(out)
@@ -196,9 +213,17 @@ class MLP(nn.Module):
         i = cfg.intermediate_size // tp_size
         self.gate_up_proj = HLinear(cfg.hidden_size, 2 * i, bias=False)
         self.down_proj = HLinear(i, cfg.hidden_size, bias=False)
+        self.lora = None               # LayerLoRA, set by LoRAManager
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        out = self.down_proj(ops.silu_and_mul(self.gate_up_proj(x)))
+    def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
+        if self.lora is None or getattr(meta, "lora_slots", None) is None:
+            out = self.down_proj(ops.silu_and_mul(self.gate_up_proj(x)))
+        else:
+            gu = _lora(self.gate_up_proj(x), x, self.lora, "gate_up_proj",
+                       meta)
+            act = ops.silu_and_mul(gu)
+            out = _lora(self.down_proj(act), act, self.lora, "down_proj",
+                        meta)
         if self.tp_size > 1:
             from helix_amd import parallel
             out = parallel.tp_all_reduce(out)
@@ -224,7 +249,7 @@ class DecoderLayer(nn.Module):
         h = self.attn(h, cos_sin, kv_cache, meta)
         h, residual = ops.fused_add_rms_norm(h, residual, self.post_norm_w,
                                              self.eps)
-        h = self.mlp(h)
+        h = self.mlp(h, meta)
         return h, residual
 
 

@@ -341,3 +341,36 @@ def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)
     return d
+
+
+def lora_shrink(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                slot: torch.Tensor) -> torch.Tensor:
+    """y[T,Rtot] (fp32, in place) = per-row A[slot[t]] @ x[t]. Rows whose
+    slot is outside [0, S) are not written."""
+    if x.is_cuda:
+        _native().lora_shrink(y, x, A, slot)
+        return y
+    return ref.lora_shrink(y, x, A, slot)
+
+
+def lora_expand(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
+                slot: torch.Tensor, scale: torch.Tensor,
+                n_off) -> torch.Tensor:
+    """out[T,N] += scale[s] * per-row B[slot[t]] @ y[t], in place. n_off is
+    a host sequence of slice boundaries (0, ..., N)."""
+    if out.is_cuda:
+        _native().lora_expand(out, y, B, slot, scale,
+                              [int(v) for v in n_off])
+        return out
+    return ref.lora_expand(out, y, B, slot, scale, n_off)
+
+
+def lora_apply(out: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+               B: torch.Tensor, slot: torch.Tensor, scale: torch.Tensor,
+               n_off) -> torch.Tensor:
+    """Shrink + expand: adds each row's adapter delta into `out` in place.
+    Rows with no adapter (slot outside [0, S)) keep `out` bit-identical."""
+    y = torch.empty(x.shape[0], A.shape[1], dtype=torch.float32,
+                    device=x.device)
+    lora_shrink(y, x, A, slot)
+    return lora_expand(out, y, B, slot, scale, n_off)

@@ -53,6 +53,11 @@ void gemm_skinny_bf16(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 void gemm_fp8(torch::Tensor out, torch::Tensor x, torch::Tensor w,
               torch::Tensor x_scale, torch::Tensor w_scale,
               c10::optional<torch::Tensor> bias, int64_t act);
+void lora_shrink(torch::Tensor y, torch::Tensor x, torch::Tensor A,
+                 torch::Tensor slot);
+void lora_expand(torch::Tensor out, torch::Tensor y, torch::Tensor B,
+                 torch::Tensor slot, torch::Tensor scale,
+                 std::vector<int64_t> n_off);
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b);
 torch::Tensor ar_create(int64_t world, int64_t rank, int64_t capacity);
 void ar_open(std::vector<torch::Tensor> handles);
@@ -88,6 +93,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Skinny-M decode GEMM: split-K + XCD-chunked tile swizzle");
   m.def("gemm_fp8", &gemm_fp8,
         "MX-fp8 e4m3 MFMA GEMM with epilogue per-row/col dequant");
+  m.def("lora_shrink", &lora_shrink,
+        "Multi-LoRA shrink: y[t] = A[slot[t]] @ x[t] (fp32 out)");
+  m.def("lora_expand", &lora_expand,
+        "Multi-LoRA expand: out[t] += scale[s] * B[s] @ y[t] (in place)");
   m.def("mfma_probe", &mfma_probe, "16x16x32 MFMA layout probe");
   m.def("ar_create", &ar_create,
         "Allocate one-shot allreduce mailbox; returns IPC handle bytes");

@@ -208,3 +208,40 @@ def gemm_bf16(x: torch.Tensor, w: torch.Tensor, bias=None,
     if act == 1:
         out = torch.nn.functional.gelu(out, approximate="tanh")
     return out.to(x.dtype)
+
+
+def lora_shrink(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                slot: torch.Tensor) -> torch.Tensor:
+    """y[t, :] = A[slot[t]] @ x[t] in fp32 for rows whose slot is in
+    [0, S); other rows of y are left untouched. x[T,K], A[S,Rtot,K],
+    y[T,Rtot] fp32 (written in place and returned)."""
+    S = A.shape[0]
+    sl = slot.long()
+    for s in torch.unique(sl).tolist():
+        if s < 0 or s >= S:
+            continue
+        rows = (sl == s).nonzero(as_tuple=True)[0]
+        y[rows] = x[rows].float() @ A[s].float().t()
+    return y
+
+
+def lora_expand(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
+                slot: torch.Tensor, scale: torch.Tensor,
+                n_off) -> torch.Tensor:
+    """out[t, n] += scale[s] * sum_j y[t, i(n)*Rmax + j] * B[s, n, j] for
+    rows whose slot s is in [0, S); other rows stay bit-identical.
+    out[T,N] (in place), y[T,Rtot] fp32, B[S,N,Rmax]; slice i owns output
+    columns [n_off[i], n_off[i+1]) and y columns [i*Rmax, (i+1)*Rmax)."""
+    S, _, R = B.shape
+    sl = slot.long()
+    for s in torch.unique(sl).tolist():
+        if s < 0 or s >= S:
+            continue
+        rows = (sl == s).nonzero(as_tuple=True)[0]
+        delta = torch.cat(
+            [y[rows, i * R:(i + 1) * R].float()
+             @ B[s, n_off[i]:n_off[i + 1]].float().t()
+             for i in range(len(n_off) - 1)], dim=1)
+        out[rows] = (out[rows].float()
+                     + scale[s].float() * delta).to(out.dtype)
+    return out

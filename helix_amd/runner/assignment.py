@@ -27,6 +27,9 @@ def apply_profile(service: RunnerService, profile: dict) -> dict:
             tp=int(m.get("tp", 1)),
             quantization=m.get("quantization"),
             kv_cache_dtype=m.get("kv_cache_dtype", "bf16"),
+            max_loras=int(m.get("max_loras", 0)),
+            max_lora_rank=int(m.get("max_lora_rank", 16)),
+            lora_dir=m.get("lora_dir"),
         )
         wanted[spec.name] = spec
         service.specs[spec.name] = spec

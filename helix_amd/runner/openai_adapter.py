@@ -96,6 +96,13 @@ async def chat_completion(service: RunnerService, req: dict,
     loop = asyncio.get_event_loop()
     inst = await loop.run_in_executor(None, service.ensure_loaded, model)
     assert isinstance(inst, LLMInstance), f"{model} is not an LLM"
+    # per-request LoRA adapter (extra body field). `model` stays the base
+    # model's name, so tokenizer/template lookup is untouched; an unknown
+    # id (or a model without adapter slots) fails like an unknown model.
+    lora = req.get("lora_id") or None
+    if lora is not None:
+        inst.resolve_lora(lora)
+    lora_kw = {"lora": lora} if lora is not None else {}
     tok = get_tokenizer(model)
     tools = req.get("tools")
     if "messages" in req and req["messages"] is not None:
@@ -114,14 +121,15 @@ async def chat_completion(service: RunnerService, req: dict,
 
     if req.get("stream"):
         return _stream(service, inst, model, rid, created, prompt_ids,
-                       params, stop_strs, tok, tools)
+                       params, stop_strs, tok, tools, **lora_kw)
 
     n = int(req.get("n") or 1)
     choices = []
     total_completion = 0
     for i in range(n):
         text, finish_reason, ntok, lp_content = await _generate_one(
-            inst, f"{rid}-{i}", prompt_ids, params, stop_strs, tok, loop)
+            inst, f"{rid}-{i}", prompt_ids, params, stop_strs, tok, loop,
+            **lora_kw)
         total_completion += ntok
         message = {"role": "assistant", "content": text}
         if tools:
@@ -153,10 +161,17 @@ async def chat_completion(service: RunnerService, req: dict,
     }
 
 
+def _submit(inst, seq_id, prompt_ids, params, on_token, lora):
+    if lora is None:
+        inst.submit(seq_id, prompt_ids, params, on_token)
+    else:
+        inst.submit(seq_id, prompt_ids, params, on_token, lora=lora)
+
+
 async def _generate_one(inst, seq_id, prompt_ids, params, stop_strs, tok,
-                        loop):
+                        loop, lora=None):
     ts = TokenStream(loop)
-    inst.submit(seq_id, prompt_ids, params, ts.on_token)
+    _submit(inst, seq_id, prompt_ids, params, ts.on_token, lora)
     detok = StreamDetokenizer(tok)
     text = ""
     finish_reason = "stop"
@@ -200,10 +215,11 @@ def _find_stop(text: str, stop_strs: List[str]) -> Optional[int]:
 
 
 async def _stream(service, inst, model, rid, created, prompt_ids, params,
-                  stop_strs, tok, tools=None) -> AsyncIterator[dict]:
+                  stop_strs, tok, tools=None,
+                  lora=None) -> AsyncIterator[dict]:
     loop = asyncio.get_event_loop()
     ts = TokenStream(loop)
-    inst.submit(rid, prompt_ids, params, ts.on_token)
+    _submit(inst, rid, prompt_ids, params, ts.on_token, lora)
     detok = StreamDetokenizer(tok)
     ntok = 0
     finished = False

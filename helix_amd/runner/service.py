@@ -41,6 +41,9 @@ class ModelSpec:
     tp: int = 1                        # tensor-parallel degree (xGMI group)
     quantization: Optional[str] = None  # None | "fp8"
     kv_cache_dtype: str = "bf16"
+    max_loras: int = 0                 # LoRA adapter slots (0 = off)
+    max_lora_rank: int = 16
+    lora_dir: Optional[str] = None     # adapters live at <lora_dir>/<lora_id>/
 
 
 DEFAULT_SPECS = {
@@ -106,7 +109,10 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
     else:
         kv = kv_block * spec.max_num_seqs * \
             (spec.max_model_len // block_size + 1)
-    return weights + kv + (1 << 30)    # +1 GiB activations/graphs headroom
+    from helix_amd.models.lora import lora_stack_bytes
+    loras = lora_stack_bytes(cfg, spec.max_loras, spec.max_lora_rank)
+    # +1 GiB activations/graphs headroom
+    return weights + kv + loras + (1 << 30)
 
 
 class LLMInstance:
@@ -129,7 +135,9 @@ class LLMInstance:
                          max_num_seqs=spec.max_num_seqs,
                          kv_cache_blocks=kv_blocks,
                          quantization=spec.quantization,
-                         kv_cache_dtype=spec.kv_cache_dtype),
+                         kv_cache_dtype=spec.kv_cache_dtype,
+                         max_loras=spec.max_loras,
+                         max_lora_rank=spec.max_lora_rank),
             device=device)
         if self.engine.graph_runner is not None:
             # eager hipGraph capture for all batch buckets (serving never
@@ -164,9 +172,13 @@ class LLMInstance:
                 return
             try:
                 if kind == "submit":
-                    seq_id, prompt_ids, params, on_token = payload
+                    seq_id, prompt_ids, params, on_token, lora = payload
+                    if lora is not None and \
+                            lora not in self.engine.list_loras():
+                        # lazy registration, on the engine thread
+                        self.engine.add_lora(lora, self.resolve_lora(lora))
                     self.engine.add_request(seq_id, prompt_ids, params,
-                                            on_token=on_token)
+                                            on_token=on_token, lora=lora)
                 elif kind == "cancel":
                     self.engine.cancel(payload)
             except Exception as e:
@@ -197,8 +209,28 @@ class LLMInstance:
                 log.exception("engine step failed (%s)", self.spec.name)
                 time.sleep(0.01)
 
+    def resolve_lora(self, lora_id: str) -> str:
+        """Adapter directory for `lora_id` (<lora_dir>/<lora_id>/). An id
+        that is not a single path component, a missing directory, or a
+        spec without adapter slots is an unknown adapter."""
+        import os
+        spec = self.spec
+        ok = (spec.max_loras > 0 and spec.lora_dir
+              and isinstance(lora_id, str) and lora_id
+              and lora_id not in (".", "..")
+              and "/" not in lora_id and "\\" not in lora_id
+              and "\0" not in lora_id
+              and os.path.basename(lora_id) == lora_id)
+        if ok:
+            path = os.path.join(spec.lora_dir, lora_id)
+            if os.path.isfile(os.path.join(path, "adapter_config.json")):
+                return path
+        raise ModelNotFoundError(
+            f"lora adapter {lora_id!r} for model {spec.name}")
+
     def submit(self, seq_id: str, prompt_ids: List[int],
-               params: SamplingParams, on_token) -> None:
+               params: SamplingParams, on_token,
+               lora: Optional[str] = None) -> None:
         if self.draining:
             if on_token is not None:
                 class _F:
@@ -209,7 +241,8 @@ class LLMInstance:
                 on_token(f, 0, True)
             return
         self.last_used = time.time()
-        self.intake.put(("submit", (seq_id, prompt_ids, params, on_token)))
+        self.intake.put(("submit", (seq_id, prompt_ids, params, on_token,
+                                    lora)))
         self.wake.set()
 
     def cancel(self, seq_id: str):

@@ -973,7 +973,10 @@ def create_app(cfg: Optional[ServerConfig] = None,
                 kv_cache_blocks=b.get("kv_cache_blocks"),
                 tp=int(b.get("tp", 1)),
                 quantization=b.get("quantization"),
-                kv_cache_dtype=b.get("kv_cache_dtype", "bf16"))
+                kv_cache_dtype=b.get("kv_cache_dtype", "bf16"),
+                max_loras=int(b.get("max_loras", 0)),
+                max_lora_rank=int(b.get("max_lora_rank", 16)),
+                lora_dir=b.get("lora_dir"))
             runner_service.register_spec(spec)
         except KeyError as e:
             raise HTTPException(400, f"missing field {e}")

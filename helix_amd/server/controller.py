@@ -134,6 +134,8 @@ class Controller:
         # the field when the assistant configures it)
         if assistant.reasoning_effort and not out.get("reasoning_effort"):
             out["reasoning_effort"] = assistant.reasoning_effort
+        if assistant.lora_id and not out.get("lora_id"):
+            out["lora_id"] = assistant.lora_id
         return out
 
     def _resolve(self, req: dict, owner: str,

@@ -79,6 +79,7 @@ class AssistantConfig(BaseModel):
     frequency_penalty: Optional[float] = None
     max_tokens: Optional[int] = None
     reasoning_effort: str = ""
+    lora_id: str = ""               # LoRA adapter served on the base model
     knowledge: List[KnowledgeSource] = []
     apis: List[ToolAPIConfig] = []
     zapier: List[Dict[str, Any]] = []
