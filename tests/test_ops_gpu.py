@@ -5,6 +5,7 @@ All marked `gpu`; run on an MI355X via gpurun. Tolerances are bf16-scale.
 import pytest
 import torch
 
+import attn_oracle as ao
 import helix_amd.ops as ops
 import helix_amd.ops.reference as ref
 
@@ -131,6 +132,8 @@ def test_attn_prefill(hq, hkv, d, lens):
     want = ref.attn_prefill(q.cpu(), k.cpu(), v.cpu(), cu.cpu(), max(lens),
                             scale)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.prefill_ref64(q, k, v, cu, scale),
+                         ao.TOL_PREFILL)
 
 
 @pytest.mark.parametrize("hq,hkv,d,lens", [
@@ -167,6 +170,8 @@ def test_paged_attn_decode(hq, hkv, d, lens):
     want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
                                  seq_lens.cpu(), scale)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.decode_ref64(q, kc, vc, bt, seq_lens, scale),
+                         ao.TOL_DECODE)
 
 
 def _paged_case(lens, hq, hkv, d, bs=16):
@@ -203,6 +208,8 @@ def test_paged_attn_decode_full_grid():
     want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
                                  seq_lens.cpu(), scale)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.decode_ref64(q, kc, vc, bt, seq_lens, scale),
+                         ao.TOL_DECODE)
 
 
 def test_decode_partition_constant():
@@ -232,21 +239,26 @@ def test_paged_attn_decode_rejects_bad_args():
     want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
                                  seq_lens.cpu(), scale)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.decode_ref64(q, kc, vc, bt, seq_lens, scale),
+                         ao.TOL_DECODE)
 
 
 def test_paged_attn_decode_partition_cap():
     """One kv head at batch 1 with a 65 600-token context: split-K sizing
     asks for 1024 partitions and the workspace allows 513; the cap of 512
     (the reduce kernel's weight array) makes it 257 partitions of 256
-    tokens."""
-    torch.manual_seed(18)
-    d = 128
-    q, kc, vc, bt, seq_lens = _paged_case([65600], 1, 1, d)
-    scale = d ** -0.5
-    got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, scale)
-    want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
-                                 seq_lens.cpu(), scale)
+    tokens. The inputs are the needle case of tests/attn_oracle.py: loud
+    keys on the edges of the first, last and two middle partitions, so a
+    lost partition or an all-zeros output fails the relative check
+    (tests/test_attn_oracle_cpu.py::test_partition_cap_can_fail)."""
+    b = ao.build_decode(ao.PARTITION_CAP_CASE)
+    assert tuple(b.q.shape) == (1, 1, 128) and int(b.lens[0]) == 65600
+    q, kc, vc, bt, seq_lens = (t.to(DEV) for t in
+                               (b.q, b.kc, b.vc, b.bt, b.lens))
+    got = ops.paged_attn_decode(q, kc, vc, bt, seq_lens, b.scale)
+    want = ref.paged_attn_decode(b.q, b.kc, b.vc, b.bt, b.lens, b.scale)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, b.want, ao.TOL_DECODE)
 
 
 def test_sample_greedy():
@@ -310,6 +322,9 @@ def test_attn_prefill_sliding_window(window, lens):
     want = ref.attn_prefill(q.cpu(), k.cpu(), v.cpu(), cu.cpu(), max(lens),
                             scale, window=window)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.prefill_ref64(q, k, v, cu, scale,
+                                               window=window),
+                         ao.TOL_PREFILL)
 
 
 @pytest.mark.parametrize("window,lens", [(64, [200]), (256, [100, 700]),
@@ -337,6 +352,9 @@ def test_paged_attn_decode_sliding_window(window, lens):
     want = ref.paged_attn_decode(q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(),
                                  seq_lens.cpu(), scale, window=window)
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.decode_ref64(q, kc, vc, bt, seq_lens, scale,
+                                              window=window),
+                         ao.TOL_DECODE)
 
 
 @pytest.mark.parametrize("qlens,klens", [([32], [160]), ([7, 64], [7, 200]),
@@ -359,6 +377,9 @@ def test_attn_prefill_cached_prefix(qlens, klens):
     want = ref.attn_prefill(q.cpu(), k.cpu(), v.cpu(), cu_q.cpu(),
                             max(qlens), scale, cu_seqlens_k=cu_k.cpu())
     assert_close_bf16(got, want, atol=3e-2, rtol=3e-2)
+    ao.assert_attn_close(got, ao.prefill_ref64(q, k, v, cu_q, scale,
+                                               cu_k=cu_k),
+                         ao.TOL_PREFILL)
 
 
 @pytest.mark.parametrize("want_kv,use_cache", [(True, True), (False, True),
@@ -503,6 +524,9 @@ def test_fp8_kv_decode_gpu(d, lens, window):
                                  lens.cpu(), scale, window=window)
     torch.testing.assert_close(out.cpu().float(), want.float(), atol=3e-2,
                                rtol=3e-2)
+    ao.assert_attn_close(out, ao.decode_ref64(q, kc, vc, bt, lens, scale,
+                                              window=window),
+                         ao.TOL_DECODE)
 
 
 def test_fp8_kv_fused_rope_write_gpu():
