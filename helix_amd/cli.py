@@ -483,10 +483,15 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
                 ckpt: str = typer.Option("", help="safetensors dir "
                                          "(random-init if empty)"),
                 out: str = typer.Option(..., "-o", "--out"),
-                seed: int = typer.Option(0)):
+                seed: int = typer.Option(0),
+                quant: str = typer.Option(
+                    "", "--quant", help="q4_0 | q8_0: quantize the "
+                    "projection weights (norms/embeddings stay as they are)")):
     """Export a model as a GGUF v3 checkpoint (llama.cpp tensor names,
     Q/K rows permuted for GGML rope — interops with the llama.cpp
     ecosystem; see engine/gguf.py)."""
+    if quant not in ("", "q4_0", "q8_0"):
+        raise typer.BadParameter("--quant must be q4_0 or q8_0")
     import torch
     from helix_amd.engine import gguf as g
     from helix_amd.models.llama import LlamaForCausalLM, PRESETS
@@ -539,6 +544,13 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
         "llama.context_length": cfg.max_position,
         "llama.rope.freq_base": float(cfg.rope_base),
     }
+    if quant:
+        proj = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate",
+                "ffn_up", "ffn_down")
+        for name, t in list(tensors.items()):
+            if name.startswith("blk.") and name.split(".")[2] in proj \
+                    and t.shape[1] % 32 == 0:
+                tensors[name] = g.quantize_ggml(t, quant.upper())
     g.write_gguf(out, meta, tensors)
     est = g.estimate_gguf_bytes(out)
     typer.echo(f"wrote {out}: {len(tensors)} tensors, "

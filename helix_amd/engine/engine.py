@@ -72,7 +72,8 @@ class EngineConfig:
     seed: int = 0
     enforce_eager: bool = False               # disable hipGraph capture
     enable_prefix_caching: bool = True
-    quantization: Optional[str] = None        # None | "fp8" (e4m3 W8A8)
+    # None | "fp8" (e4m3 W8A8) | "q4_0" | "q8_0" (ggml weight-only)
+    quantization: Optional[str] = None
     kv_cache_dtype: str = "bf16"              # "bf16" | "fp8" (e4m3 KV)
     max_loras: int = 0                        # adapter slots (0 = LoRA off)
     max_lora_rank: int = 16
@@ -97,6 +98,17 @@ class LLMEngine:
         if cfg.quantization == "fp8":
             from helix_amd.models.quant import quantize_model_fp8
             quantize_model_fp8(model)
+        elif cfg.quantization in ("q4_0", "q8_0"):
+            # weight-only ggml blocks; a model that already holds
+            # WQLinears (resident GGUF load) is served as it is
+            from helix_amd.models.quant import has_wq, quantize_model_wq
+            if not has_wq(model):
+                quantize_model_wq(model, cfg.quantization)
+        # a model holding WQLinears (quantized above, or loaded resident
+        # from GGUF and perhaps moved since) owns its dequant scratch;
+        # a no-op for every other model
+        from helix_amd.models.quant import attach_wq_scratch
+        attach_wq_scratch(model)
         self.model = model
         # per-request LoRA adapters: device-resident slot stacks hooked
         # into the attention / MLP projections (models/lora.py)

@@ -8,9 +8,14 @@ fused-projection layout (models/llama.py), un-permute the Q/K rope
 reordering applied by llama.cpp's HF converter, and dequantize
 F32/F16/BF16/Q8_0/Q4_0 tensors straight into bf16 device weights.
 
-Quantized *serving* (keeping Q-weights resident and dequantizing in the
-GEMM) is a round-2 item; this module makes GGUF checkpoints loadable and
-sizeable today.
+Quantized *serving*: `load_gguf_weights(..., keep_quantized=True)` keeps
+Q4_0/Q8_0 projections resident as the file's own blocks (a strided copy
+into the two-plane device layout of ops/hip/gemm_wq.hip, no re-encoding)
+and serves them through models/quant.py WQLinear, which dequantizes inside
+the GEMM. Everything else, including projections of mixed or unsupported
+types, is dequantized to the model dtype as before. `write_gguf` accepts
+pre-quantized `GGMLQuantized` tensors so `helix export-gguf --quant` (and
+the tests) can produce such files. K-quants stay estimation-only.
 """
 from __future__ import annotations
 
@@ -56,6 +61,24 @@ GGML_TYPES: Dict[int, Tuple[str, int, int]] = {
     30: ("BF16", 1, 2),
 }
 _NAME_TO_GGML = {v[0]: k for k, v in GGML_TYPES.items()}
+
+# ggml type name <-> ops weight-only format string
+_WQ_FMT = {"Q4_0": "q4_0", "Q8_0": "q8_0"}
+
+
+class GGMLQuantized(NamedTuple):
+    """A tensor already in ggml block bytes, for write_gguf."""
+    raw: bytes
+    shape: Tuple[int, ...]   # torch order ([out, in])
+    type_name: str           # key of GGML_TYPES by name, e.g. "Q4_0"
+
+
+def quantize_ggml(w: torch.Tensor, type_name: str) -> GGMLQuantized:
+    """Quantize a [N, K] weight with ggml's reference Q4_0/Q8_0 quantizer."""
+    from helix_amd import ops
+    fmt = _WQ_FMT[type_name]
+    qs, d = ops.quantize_wq(w, fmt)
+    return GGMLQuantized(ops.pack_ggml(qs, d, fmt), tuple(w.shape), type_name)
 
 
 class GGUFTensorInfo(NamedTuple):
@@ -287,24 +310,45 @@ def _write_value(f: BinaryIO, v: Any):
 
 
 def write_gguf(path: str, metadata: Dict[str, Any],
-               tensors: Dict[str, torch.Tensor], align: int = 32):
-    """Write a GGUF v3 file (F32/F16/BF16 payloads). Used by tests and
-    `helix export-gguf`; quantized writing is out of scope."""
-    infos: List[Tuple[str, torch.Tensor, int, int]] = []
+               tensors: Dict[str, Any], align: int = 32):
+    """Write a GGUF v3 file. Values are torch tensors (F32/F16/BF16
+    payloads) or GGMLQuantized (block bytes written as they are). Used by
+    tests and `helix export-gguf`."""
+    # (name, payload bytes, torch-order shape, ggml type, offset)
+    infos: List[Tuple[str, bytes, Tuple[int, ...], int, int]] = []
     off = 0
     for name, t in tensors.items():
-        t = t.detach().cpu().contiguous()
-        if t.dtype == torch.float32:
-            gt = _NAME_TO_GGML["F32"]
-        elif t.dtype == torch.float16:
-            gt = _NAME_TO_GGML["F16"]
-        elif t.dtype == torch.bfloat16:
-            gt = _NAME_TO_GGML["BF16"]
+        if isinstance(t, GGMLQuantized):
+            if t.type_name not in _NAME_TO_GGML:
+                raise TypeError(f"{name}: unknown ggml type {t.type_name}")
+            gt = _NAME_TO_GGML[t.type_name]
+            _, blk, bsz = GGML_TYPES[gt]
+            numel = 1
+            for dim in t.shape:
+                numel *= dim
+            if not t.shape or t.shape[-1] % blk or \
+                    len(t.raw) != numel // blk * bsz:
+                raise ValueError(
+                    f"{name}: {len(t.raw)} bytes do not match shape "
+                    f"{tuple(t.shape)} of {t.type_name}")
+            buf, shape = bytes(t.raw), tuple(t.shape)
         else:
-            raise TypeError(f"{name}: dtype {t.dtype} not writable")
-        nbytes = t.numel() * t.element_size()
-        infos.append((name, t, gt, off))
-        off += (nbytes + align - 1) // align * align
+            t = t.detach().cpu().contiguous()
+            if t.dtype == torch.float32:
+                gt = _NAME_TO_GGML["F32"]
+            elif t.dtype == torch.float16:
+                gt = _NAME_TO_GGML["F16"]
+            elif t.dtype == torch.bfloat16:
+                gt = _NAME_TO_GGML["BF16"]
+            else:
+                raise TypeError(f"{name}: dtype {t.dtype} not writable")
+            if t.dtype == torch.bfloat16:
+                buf = t.view(torch.uint16).numpy().tobytes()
+            else:
+                buf = t.numpy().tobytes()
+            shape = tuple(t.shape)
+        infos.append((name, buf, shape, gt, off))
+        off += (len(buf) + align - 1) // align * align
     with open(path, "wb") as f:
         f.write(GGUF_MAGIC)
         f.write(struct.pack("<I", 3))
@@ -314,36 +358,104 @@ def write_gguf(path: str, metadata: Dict[str, Any],
         for k, v in meta.items():
             _write_str(f, k)
             _write_value(f, v)
-        for name, t, gt, o in infos:
+        for name, buf, shape, gt, o in infos:
             _write_str(f, name)
-            dims = tuple(reversed(t.shape)) if t.dim() else (1,)
+            dims = tuple(reversed(shape)) if shape else (1,)
             f.write(struct.pack("<I", len(dims)))
             f.write(struct.pack(f"<{len(dims)}Q", *dims))
             f.write(struct.pack("<I", gt))
             f.write(struct.pack("<Q", o))
         pos = f.tell()
         f.write(b"\x00" * ((pos + align - 1) // align * align - pos))
-        for name, t, gt, o in infos:
-            if t.dtype == torch.bfloat16:
-                buf = t.view(torch.uint16).numpy().tobytes()
-            else:
-                buf = t.numpy().tobytes()
+        for name, buf, shape, gt, o in infos:
             f.write(buf)
             pad = (len(buf) + align - 1) // align * align - len(buf)
             f.write(b"\x00" * pad)
 
 
+# fused projection -> (GGUF part suffixes in row order, role per part)
+_FUSED_PARTS = {
+    "attn.qkv_proj": (("attn_q", "q"), ("attn_k", "k"), ("attn_v", "v")),
+    "attn.o_proj": (("attn_output", None),),
+    "mlp.gate_up_proj": (("ffn_gate", "gate"), ("ffn_up", "up")),
+    "mlp.down_proj": (("ffn_down", None),),
+}
+
+
+def _install_resident(model, g: GGUFFile) -> set:
+    """Install every projection whose GGUF parts are all the same one of
+    Q4_0/Q8_0 as a WQLinear holding the file's blocks. Returns the GGUF
+    tensor names consumed."""
+    from helix_amd import ops
+    from helix_amd.models.quant import WQLinear, attach_wq_scratch
+    cfg = model.cfg
+    todo = []
+    for i in range(cfg.num_layers):
+        for proj, parts in _FUSED_PARTS.items():
+            names = [f"blk.{i}.{p}.weight" for p, _ in parts]
+            if not all(n in g.tensors for n in names):
+                continue
+            types = {g.tensors[n].type_name for n in names}
+            if len(types) != 1 or next(iter(types)) not in _WQ_FMT:
+                continue
+            owner = model.get_submodule(f"layers.{i}.{proj.split('.')[0]}")
+            lin = getattr(owner, proj.split(".")[1])
+            if not isinstance(lin, torch.nn.Linear):
+                continue
+            infos = [g.tensors[n] for n in names]
+            if any(len(t.shape) != 2 or t.shape[1] != lin.in_features
+                   for t in infos) or \
+                    sum(t.shape[0] for t in infos) != lin.out_features or \
+                    lin.in_features % 32 or lin.out_features % 16:
+                continue
+            todo.append((owner, proj.split(".")[1], lin, names, parts,
+                         _WQ_FMT[next(iter(types))]))
+    if not todo:
+        return set()
+    dev = todo[0][2].weight.device
+    used = set()
+    for owner, attr, lin, names, parts, fmt in todo:
+        qs_parts, d_parts = [], []
+        for n, (_, role) in zip(names, parts):
+            qs, d = ops.unpack_ggml(g.read_raw(n), g.tensors[n].shape, fmt)
+            # a block never crosses a row, so the Q/K row permutation
+            # applies to the planes as whole rows
+            if role == "q":
+                qs, d = (unpermute_rope(qs, cfg.num_heads),
+                         unpermute_rope(d, cfg.num_heads))
+            elif role == "k":
+                qs, d = (unpermute_rope(qs, cfg.num_kv_heads),
+                         unpermute_rope(d, cfg.num_kv_heads))
+            qs_parts.append(qs)
+            d_parts.append(d)
+            used.add(n)
+        # the bias stays the model's own: map_gguf_name maps no bias tensor
+        # today; when it does, the loader must write WQLinear.bias, which
+        # is a buffer and not among named_parameters()
+        bias = None if lin.bias is None else lin.bias.data
+        setattr(owner, attr, WQLinear(
+            torch.cat(qs_parts, dim=0).contiguous().to(dev),
+            torch.cat(d_parts, dim=0).contiguous().to(dev), fmt, bias))
+    attach_wq_scratch(model)
+    return used
+
+
 @torch.inference_mode()
-def load_gguf_weights(model, path: str) -> int:
+def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     """Load a GGUF llama checkpoint into a helix_amd Llama model
-    (dequantizing to the model dtype; Q/K rope rows un-permuted)."""
+    (dequantizing to the model dtype; Q/K rope rows un-permuted). With
+    keep_quantized, Q4_0/Q8_0 projections stay resident as the file's
+    blocks (WQLinear); see the module docstring."""
     g = GGUFFile(path)
+    resident = _install_resident(model, g) if keep_quantized else set()
     params = dict(model.named_parameters())
     cfg = model.cfg
     q, kv = cfg.q_size, cfg.kv_size
     inter = cfg.intermediate_size
-    loaded = 0
+    loaded = len(resident)
     for name in g.tensors:
+        if name in resident:
+            continue
         our, role = map_gguf_name(name)
         if our not in params:
             continue

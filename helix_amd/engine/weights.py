@@ -103,11 +103,14 @@ def _map_hf_name(name: str):
 
 
 @torch.inference_mode()
-def load_llama_weights(model, ckpt_dir: str, use_async: bool = True):
+def load_llama_weights(model, ckpt_dir: str, use_async: bool = True,
+                       keep_quantized: bool = False):
     """Load a Llama checkpoint (HF layout or our native layout) into the
     model. On GPU, tensors are staged through a pinned-host buffer and
     copied on a side stream (hipMemcpyAsync) so decode streams on the
-    default stream are not serialized behind weight traffic."""
+    default stream are not serialized behind weight traffic.
+    keep_quantized applies to GGUF checkpoints only: Q4_0/Q8_0 projections
+    stay resident as the file's blocks (engine/gguf.py)."""
     # GGUF checkpoints (llama.cpp ecosystem) route through the native
     # GGUF loader (engine/gguf.py): file path or a dir holding one.
     gguf_path = None
@@ -119,7 +122,8 @@ def load_llama_weights(model, ckpt_dir: str, use_async: bool = True):
             gguf_path = ggufs[0]
     if gguf_path is not None:
         from . import gguf as _gguf
-        n = _gguf.load_gguf_weights(model, gguf_path)
+        n = _gguf.load_gguf_weights(model, gguf_path,
+                                    keep_quantized=keep_quantized)
         log.info("loaded %d tensors from GGUF %s", n, gguf_path)
         return n
 

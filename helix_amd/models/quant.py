@@ -1,5 +1,5 @@
-"""Weights-quantized serving (fp8 e4m3, W8A8 with per-channel/per-token
-scales).
+"""Weights-quantized serving: fp8 e4m3 W8A8 with per-channel/per-token
+scales, and weight-only ggml Q4_0/Q8_0 (second half of this file).
 
 The reference serves quantized checkpoints through vLLM/Ollama
 quantization support; here quantization is a
@@ -62,3 +62,121 @@ def quantize_model_fp8(model: nn.Module,
             setattr(mod, child_name, FP8Linear.from_linear(child))
             converted += 1
     return converted
+
+
+# -- weight-only ggml Q4_0 / Q8_0 (ops/hip/gemm_wq.hip) -----------------
+# Unlike the fp8 pass above this keeps activations bf16 and the weights in
+# ggml's own blocks (32 along K, one fp16 scale): a GGUF file's blocks are
+# served as they are on disk (engine/gguf.py keep_quantized), or a dense
+# model is quantized after load with ggml's reference quantizer.
+
+class WQLinear(nn.Module):
+    """Drop-in nn.Linear replacement holding ggml Q4_0/Q8_0 planes:
+    `qs` (payload bytes) and `d` (fp16 block scales), plus an optional
+    bias. Up to ops.WQ_FUSED_MAX_M rows run the fused dequant GEMM; larger
+    batches dequantize into `scratch` and use the library GEMM.
+
+    `scratch` is a bf16 buffer owned by the MODEL this module belongs to
+    (attach_wq_scratch): its layers run one after another on one stream
+    and may share it, two models may not, because the large-M path is two
+    launches (dequantize, GEMM) that another model's thread can get
+    between. Without one the large-M path allocates per call."""
+
+    def __init__(self, qs: torch.Tensor, d: torch.Tensor, fmt: str,
+                 bias: torch.Tensor | None = None,
+                 scratch: torch.Tensor | None = None):
+        super().__init__()
+        bits = ops.wq_bits(fmt)
+        self.fmt = fmt
+        self.register_buffer("qs", qs.contiguous(), persistent=True)
+        self.register_buffer("d", d.contiguous(), persistent=True)
+        if bias is not None:
+            self.register_buffer("bias", bias.contiguous(), persistent=True)
+        else:
+            self.bias = None
+        self.out_features = qs.shape[0]
+        self.in_features = qs.shape[1] * 2 if bits == 4 else qs.shape[1]
+        if d.dtype != torch.float16 or \
+                tuple(d.shape) != (self.out_features, self.in_features // 32):
+            raise ValueError(
+                f"WQLinear: d is {d.dtype} {tuple(d.shape)}, expected fp16 "
+                f"{(self.out_features, self.in_features // 32)}")
+        self.scratch = scratch
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear, fmt: str) -> "WQLinear":
+        qs, d = ops.quantize_wq(lin.weight.data, fmt)
+        bias = None if lin.bias is None else lin.bias.data
+        return cls(qs, d, fmt, bias)
+
+    def _apply(self, fn, recurse=True):
+        # model.to(dtype) / .half() / .bfloat16() convert every floating
+        # buffer; the block scales are fp16 by format, so `d` follows the
+        # device only. A scratch left on another device is dropped
+        # (attach_wq_scratch gives the model a new one).
+        d = self.d
+        super()._apply(fn, recurse)
+        if self.d.dtype != torch.float16:
+            self.d = d.to(self.d.device)
+        if self.scratch is not None and self.scratch.device != self.qs.device:
+            self.scratch = None
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape[:-1]
+        x2 = x.reshape(-1, self.in_features)
+        if x2.is_cuda and not x2.is_contiguous():
+            x2 = x2.contiguous()
+        out = ops.gemm_wq(x2, self.qs, self.d, self.fmt, self.bias,
+                          scratch=self.scratch)
+        return out.reshape(*shape, self.out_features)
+
+
+def attach_wq_scratch(model: nn.Module) -> None:
+    """Give `model` its own dequant buffer: one bf16 tensor per GPU it has
+    WQLinears on, sized for the largest of them and shared by them alone.
+    Called when the weights are installed and again by the engine if the
+    model was moved since; never from a forward. A model whose modules
+    already hold a fitting buffer is left as it is (captured graphs point
+    into it)."""
+    mods = [m for m in model.modules()
+            if isinstance(m, WQLinear) and m.qs.is_cuda]
+    need: dict = {}
+    for m in mods:
+        n = m.in_features * m.out_features
+        need[m.qs.device] = max(need.get(m.qs.device, 0), n)
+    for dev, numel in need.items():
+        mine = [m for m in mods if m.qs.device == dev]
+        cur = mine[0].scratch
+        if cur is not None and cur.device == dev and cur.numel() >= numel \
+                and all(m.scratch is cur for m in mine):
+            continue
+        buf = torch.empty(numel, dtype=torch.bfloat16, device=dev)
+        for m in mine:
+            m.scratch = buf
+
+
+def quantize_model_wq(model: nn.Module, fmt: str,
+                      skip: tuple = ("lm_head",)) -> int:
+    """Swap eligible Linears (in_features % 32 == 0, out_features % 16 == 0,
+    name outside `skip`; a bias is kept) for WQLinear, then give the model
+    its dequant scratch. Returns the number of modules converted."""
+    ops.wq_bits(fmt)
+    converted = 0
+    for name, mod in list(model.named_modules()):
+        for child_name, child in list(mod.named_children()):
+            full = f"{name}.{child_name}" if name else child_name
+            if not isinstance(child, nn.Linear):
+                continue
+            if any(s in full for s in skip):
+                continue
+            if child.in_features % 32 != 0 or child.out_features % 16 != 0:
+                continue
+            setattr(mod, child_name, WQLinear.from_linear(child, fmt))
+            converted += 1
+    attach_wq_scratch(model)
+    return converted
+
+
+def has_wq(model: nn.Module) -> bool:
+    return any(isinstance(m, WQLinear) for m in model.modules())

@@ -337,6 +337,69 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
     return torch.nn.functional.linear(x, w, bias)
 
 
+# -- ggml Q4_0 / Q8_0 weight-only GEMM (ops/hip/gemm_wq.hip) ------------
+from .reference import (quantize_wq, dequantize_wq, pack_ggml,  # noqa: E402,F401
+                        unpack_ggml, wq_bits, WQ_FORMATS)
+
+# Largest M the fused dequant+MFMA kernel serves; above it the weight is
+# dequantized into a scratch buffer and the library GEMM runs. Must be a
+# member of graph_runner.BATCH_BUCKETS so a batch and its padded bucket
+# take the same path (tests/test_wq_cpu.py holds that). The kernel itself
+# goes to 64 (_C.WQ_KERNEL_MAX_M); 16 is the largest bucket at which it
+# still beats the bf16 library GEMM at the llama3-8b projection shapes
+# (profiles/r05_wq.md: 0.99-2.4x at M = 16, 0.81-1.8x at M = 32).
+WQ_FUSED_MAX_M = 16
+
+
+def dequant_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Planes -> bf16 [N, K]. GPU: the HIP kernel, into `out` when given
+    (any contiguous bf16 buffer of at least N*K elements). CPU: the torch
+    reference, `out` unused."""
+    bits = wq_bits(fmt)
+    if not qs.is_cuda:
+        return dequantize_wq(qs, d, fmt, torch.bfloat16)
+    N = qs.shape[0]
+    K = qs.shape[1] * 2 if bits == 4 else qs.shape[1]
+    if out is None:
+        w = torch.empty(N, K, dtype=torch.bfloat16, device=qs.device)
+    else:
+        if out.dtype != torch.bfloat16 or out.numel() < N * K \
+                or not out.is_contiguous():
+            raise ValueError(
+                f"dequant_wq: scratch must be contiguous bf16 with at least "
+                f"{N * K} elements, got {out.dtype} x {out.numel()}")
+        w = out.view(-1)[:N * K].view(N, K)
+    _native().dequant_wq(w, qs, d, bits)
+    return w
+
+
+def gemm_wq(x: torch.Tensor, qs: torch.Tensor, d: torch.Tensor, fmt: str,
+            bias: torch.Tensor | None = None,
+            scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """out[M,N] = x[M,K] @ dequant(qs, d)^T (+ bias): ggml Q4_0/Q8_0
+    weights kept quantized. GPU, M <= WQ_FUSED_MAX_M: dequant fused into the
+    MFMA loop. GPU, larger M: dequant_wq into `scratch` (allocated per call
+    when None, so capture-safe callers pass one) + the library GEMM.
+    CPU: F.linear on the dequantized weight, the definition tests hold the
+    rest of the stack to."""
+    bits = wq_bits(fmt)
+    if not x.is_cuda:
+        w = dequantize_wq(qs, d, fmt, torch.float32).to(x.dtype)
+        return torch.nn.functional.linear(x, w, bias)
+    if x.dim() != 2:
+        raise ValueError(f"gemm_wq: x must be [M, K], got {tuple(x.shape)}")
+    M, N = x.shape[0], qs.shape[0]
+    if 0 < M <= WQ_FUSED_MAX_M:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        _native().gemm_wq(out, x, qs, d, bias, bits)
+        return out
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"gemm_wq: x must be bf16 on GPU, got {x.dtype}")
+    w = dequant_wq(qs, d, fmt, out=scratch)
+    return torch.nn.functional.linear(x, w, bias)
+
+
 def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)

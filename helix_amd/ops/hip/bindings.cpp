@@ -58,6 +58,12 @@ void lora_shrink(torch::Tensor y, torch::Tensor x, torch::Tensor A,
 void lora_expand(torch::Tensor out, torch::Tensor y, torch::Tensor B,
                  torch::Tensor slot, torch::Tensor scale,
                  std::vector<int64_t> n_off);
+void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
+             torch::Tensor d, c10::optional<torch::Tensor> bias,
+             int64_t bits);
+void dequant_wq(torch::Tensor out, torch::Tensor qs, torch::Tensor d,
+                int64_t bits);
+int64_t wq_kernel_max_m();
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b);
 torch::Tensor ar_create(int64_t world, int64_t rank, int64_t capacity);
 void ar_open(std::vector<torch::Tensor> handles);
@@ -97,6 +103,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Multi-LoRA shrink: y[t] = A[slot[t]] @ x[t] (fp32 out)");
   m.def("lora_expand", &lora_expand,
         "Multi-LoRA expand: out[t] += scale[s] * B[s] @ y[t] (in place)");
+  m.def("gemm_wq", &gemm_wq,
+        "Q4_0/Q8_0 weight-only GEMM, dequant fused into the MFMA loop (M <= 64)");
+  m.def("dequant_wq", &dequant_wq,
+        "Q4_0/Q8_0 planes -> bf16 [N,K] into a caller buffer");
+  m.attr("WQ_KERNEL_MAX_M") = wq_kernel_max_m();
   m.def("mfma_probe", &mfma_probe, "16x16x32 MFMA layout probe");
   m.def("ar_create", &ar_create,
         "Allocate one-shot allreduce mailbox; returns IPC handle bytes");

@@ -245,3 +245,92 @@ def lora_expand(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
         out[rows] = (out[rows].float()
                      + scale[s].float() * delta).to(out.dtype)
     return out
+
+
+# -- ggml Q4_0 / Q8_0 weight-only formats -------------------------------
+# Blocks of 32 consecutive elements along K with one fp16 scale each.
+# Device layout is two planes: the blocks' payload bytes, unchanged and in
+# order (qs: uint8 [N, K/2] for q4_0, int8 [N, K] for q8_0) and the scales
+# (d: fp16 [N, K/32]).
+
+WQ_BLOCK = 32
+WQ_FORMATS = {"q4_0": (4, 16, 18), "q8_0": (8, 32, 34)}   # bits, payload, block
+
+
+def wq_bits(fmt: str) -> int:
+    if fmt not in WQ_FORMATS:
+        raise ValueError(f"unknown weight-only format {fmt!r} "
+                         f"(expected one of {sorted(WQ_FORMATS)})")
+    return WQ_FORMATS[fmt][0]
+
+
+def quantize_wq(w: torch.Tensor, fmt: str):
+    """ggml's reference quantizer. w [N, K] -> (qs, d) planes."""
+    bits = wq_bits(fmt)
+    if w.dim() != 2 or w.shape[1] % WQ_BLOCK:
+        raise ValueError(f"quantize_wq: need [N, K] with K % 32 == 0, "
+                         f"got {tuple(w.shape)}")
+    N, K = w.shape
+    x = w.detach().float().reshape(N, K // WQ_BLOCK, WQ_BLOCK)
+    if bits == 4:
+        idx = x.abs().argmax(dim=-1, keepdim=True)
+        mx = x.gather(-1, idx)                  # signed, largest magnitude
+        d = mx / -8.0
+        inv = torch.where(d != 0, 1.0 / d, torch.zeros_like(d))
+        nib = (x * inv + 8.5).to(torch.int32).clamp_(max=15)   # truncation
+        nib = nib.to(torch.uint8)
+        qs = (nib[..., :16] | (nib[..., 16:] << 4)).reshape(N, K // 2)
+    else:
+        d = x.abs().amax(dim=-1, keepdim=True) / 127.0
+        inv = torch.where(d != 0, 1.0 / d, torch.zeros_like(d))
+        v = x * inv
+        q = torch.sign(v) * torch.floor(v.abs() + 0.5)         # roundf
+        qs = q.to(torch.int8).reshape(N, K)
+    return qs.contiguous(), d.squeeze(-1).to(torch.float16).contiguous()
+
+
+def dequantize_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planes -> [N, K]: d * (nib - 8) resp. d * q in fp32, one rounding
+    to `dtype`."""
+    bits = wq_bits(fmt)
+    N, nblk = d.shape
+    df = d.float().unsqueeze(-1)
+    if bits == 4:
+        b = qs.reshape(N, nblk, 16)
+        q = torch.cat([b & 0x0F, b >> 4], dim=-1).float() - 8.0
+    else:
+        q = qs.reshape(N, nblk, 32).float()
+    return (df * q).reshape(N, nblk * WQ_BLOCK).to(dtype)
+
+
+def pack_ggml(qs: torch.Tensor, d: torch.Tensor, fmt: str) -> bytes:
+    """Planes -> ggml block bytes (fp16 d, then the payload, per block)."""
+    wq_bits(fmt)
+    payload = WQ_FORMATS[fmt][1]
+    N, nblk = d.shape
+    db = d.detach().cpu().contiguous().view(torch.uint8).reshape(N, nblk, 2)
+    qb = qs.detach().cpu().contiguous().view(torch.uint8).reshape(
+        N, nblk, payload)
+    return torch.cat([db, qb], dim=-1).contiguous().numpy().tobytes()
+
+
+def unpack_ggml(raw, shape, fmt: str):
+    """ggml block bytes of a [N, K] tensor -> (qs, d) planes: a strided
+    copy, no re-encoding."""
+    bits = wq_bits(fmt)
+    _, payload, blk = WQ_FORMATS[fmt]
+    N, K = shape
+    if K % WQ_BLOCK:
+        raise ValueError(f"unpack_ggml: K={K} is not a multiple of 32")
+    nblk = K // WQ_BLOCK
+    buf = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+    if buf.numel() != N * nblk * blk:
+        raise ValueError(f"unpack_ggml: {buf.numel()} bytes for shape "
+                         f"{tuple(shape)} {fmt}, expected {N * nblk * blk}")
+    b = buf.reshape(N, nblk, blk)
+    d = b[..., :2].contiguous().view(torch.float16).reshape(N, nblk)
+    qs = b[..., 2:].contiguous().reshape(N, nblk * payload)
+    if bits == 8:
+        qs = qs.view(torch.int8)
+    return qs, d

@@ -60,6 +60,9 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=32)
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--variants", default="",
+                    help="comma-separated extra variants to add to the "
+                         "default set: q4_0, q8_0 (ggml weight-only)")
     args = ap.parse_args()
 
     from helix_amd.models.llama import PRESETS
@@ -80,6 +83,10 @@ def main():
         "fp8_kv": {"kv_cache_dtype": "fp8"},
         "fp8_both": {"quantization": "fp8", "kv_cache_dtype": "fp8"},
     }
+    for extra in filter(None, args.variants.split(",")):
+        if extra not in ("q4_0", "q8_0"):
+            ap.error(f"unknown variant {extra!r} (q4_0, q8_0)")
+        variants[extra] = {"quantization": extra}
     ref_tokens = None
     ref_logits = logit_probe(base, args.device, prompts[0])
     report = {}
