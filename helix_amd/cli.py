@@ -485,13 +485,16 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
                 out: str = typer.Option(..., "-o", "--out"),
                 seed: int = typer.Option(0),
                 quant: str = typer.Option(
-                    "", "--quant", help="q4_0 | q8_0: quantize the "
-                    "projection weights (norms/embeddings stay as they are)")):
+                    "", "--quant", help="q4_0 | q8_0 | q4_k | q6_k: quantize "
+                    "the projection weights (norms/embeddings stay as they "
+                    "are); q4_k_m: llama.cpp's Q4_K/Q6_K mix, output.weight "
+                    "Q6_K and token_embd Q4_K")):
     """Export a model as a GGUF v3 checkpoint (llama.cpp tensor names,
     Q/K rows permuted for GGML rope — interops with the llama.cpp
     ecosystem; see engine/gguf.py)."""
-    if quant not in ("", "q4_0", "q8_0"):
-        raise typer.BadParameter("--quant must be q4_0 or q8_0")
+    if quant not in ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m"):
+        raise typer.BadParameter(
+            "--quant must be q4_0, q8_0, q4_k, q6_k or q4_k_m")
     import torch
     from helix_amd.engine import gguf as g
     from helix_amd.models.llama import LlamaForCausalLM, PRESETS
@@ -547,10 +550,25 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
     if quant:
         proj = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate",
                 "ffn_up", "ffn_down")
+        block = 256 if quant.endswith(("_k", "_k_m")) else 32
         for name, t in list(tensors.items()):
-            if name.startswith("blk.") and name.split(".")[2] in proj \
-                    and t.shape[1] % 32 == 0:
-                tensors[name] = g.quantize_ggml(t, quant.upper())
+            if not (name.startswith("blk.") and name.split(".")[2] in proj
+                    and t.shape[1] % block == 0):
+                continue
+            gtype = quant.upper()
+            if quant == "q4_k_m":
+                # llama.cpp's recipe: Q4_K, with Q6_K for attn_v and
+                # ffn_down in the layers q4_k_m_uses_q6_k selects
+                part, layer = name.split(".")[2], int(name.split(".")[1])
+                more = part in ("attn_v", "ffn_down") and \
+                    g.q4_k_m_uses_q6_k(layer, cfg.num_layers)
+                gtype = "Q6_K" if more else "Q4_K"
+            tensors[name] = g.quantize_ggml(t, gtype)
+        if quant == "q4_k_m":
+            for name, gtype in (("output.weight", "Q6_K"),
+                                ("token_embd.weight", "Q4_K")):
+                if tensors[name].shape[1] % 256 == 0:
+                    tensors[name] = g.quantize_ggml(tensors[name], gtype)
     g.write_gguf(out, meta, tensors)
     est = g.estimate_gguf_bytes(out)
     typer.echo(f"wrote {out}: {len(tensors)} tensors, "

@@ -72,7 +72,8 @@ class EngineConfig:
     seed: int = 0
     enforce_eager: bool = False               # disable hipGraph capture
     enable_prefix_caching: bool = True
-    # None | "fp8" (e4m3 W8A8) | "q4_0" | "q8_0" (ggml weight-only)
+    # None | "fp8" (e4m3 W8A8) | "q4_0" | "q8_0" | "q4_k" | "q6_k" (ggml
+    # weight-only)
     quantization: Optional[str] = None
     kv_cache_dtype: str = "bf16"              # "bf16" | "fp8" (e4m3 KV)
     max_loras: int = 0                        # adapter slots (0 = LoRA off)
@@ -98,9 +99,9 @@ class LLMEngine:
         if cfg.quantization == "fp8":
             from helix_amd.models.quant import quantize_model_fp8
             quantize_model_fp8(model)
-        elif cfg.quantization in ("q4_0", "q8_0"):
+        elif cfg.quantization in ("q4_0", "q8_0", "q4_k", "q6_k"):
             # weight-only ggml blocks; a model that already holds
-            # WQLinears (resident GGUF load) is served as it is
+            # WQLinears / KQLinears (resident GGUF load) is served as it is
             from helix_amd.models.quant import has_wq, quantize_model_wq
             if not has_wq(model):
                 quantize_model_wq(model, cfg.quantization)

@@ -6,16 +6,30 @@ llama.cpp containers; here GGUF is a first-class *input format* for the
 native engine: we parse the header, map llama.cpp tensor names onto our
 fused-projection layout (models/llama.py), un-permute the Q/K rope
 reordering applied by llama.cpp's HF converter, and dequantize
-F32/F16/BF16/Q8_0/Q4_0 tensors straight into bf16 device weights.
+F32/F16/BF16/Q8_0/Q4_0/Q4_K/Q5_K/Q6_K tensors straight into bf16 device
+weights, so a Q4_K_M or Q5_K_M file loads dense, embeddings and
+output.weight included.
 
 Quantized *serving*: `load_gguf_weights(..., keep_quantized=True)` keeps
-Q4_0/Q8_0 projections resident as the file's own blocks (a strided copy
-into the two-plane device layout of ops/hip/gemm_wq.hip, no re-encoding)
-and serves them through models/quant.py WQLinear, which dequantizes inside
-the GEMM. Everything else, including projections of mixed or unsupported
-types, is dequantized to the model dtype as before. `write_gguf` accepts
-pre-quantized `GGMLQuantized` tensors so `helix export-gguf --quant` (and
-the tests) can produce such files. K-quants stay estimation-only.
+projections resident as the file's own blocks (a strided copy into the
+plane layouts of ops/hip/gemm_wq.hip and ops/hip/gemm_kq.hip, no
+re-encoding) and dequantizes them inside the GEMM:
+  * a projection whose parts are all Q4_0 or all Q8_0 becomes a
+    models/quant.py WQLinear;
+  * a projection whose parts are each Q4_K or Q6_K becomes a KQLinear with
+    one segment per part; the parts may differ in type (a Q4_K_M file's
+    qkv_proj is Q4_K, Q4_K, Q6_K). It needs K % 256 == 0 and every part's
+    N % 16 == 0.
+Everything else, including any other mix of types (Q4_0 with Q8_0, a
+K-quant part next to a legacy or float part) and Q5_K, is dequantized to
+the model dtype as before. `write_gguf` accepts pre-quantized
+`GGMLQuantized` tensors so `helix export-gguf --quant` (and the tests) can
+produce such files.
+
+The K-quant decoders follow ggml's block_q4_K / block_q5_K / block_q6_K and
+dequantize_row_* as written down in docs/KERNELS.md; no file written by
+llama.cpp has been read with them yet. Q2_K/Q3_K and the IQ types stay
+estimation-only.
 """
 from __future__ import annotations
 
@@ -64,6 +78,8 @@ _NAME_TO_GGML = {v[0]: k for k, v in GGML_TYPES.items()}
 
 # ggml type name <-> ops weight-only format string
 _WQ_FMT = {"Q4_0": "q4_0", "Q8_0": "q8_0"}
+# ggml type name <-> ops K-quant format string (resident types only)
+_KQ_FMT = {"Q4_K": "q4_k", "Q6_K": "q6_k"}
 
 
 class GGMLQuantized(NamedTuple):
@@ -73,9 +89,21 @@ class GGMLQuantized(NamedTuple):
     type_name: str           # key of GGML_TYPES by name, e.g. "Q4_0"
 
 
+def q4_k_m_uses_q6_k(layer: int, n_layers: int) -> bool:
+    """llama.cpp's Q4_K_M recipe: the layers whose attn_v and ffn_down are
+    Q6_K instead of Q4_K (integer division, as in use_more_bits)."""
+    return (layer < n_layers // 8 or layer >= 7 * n_layers // 8
+            or (layer - n_layers // 8) % 3 == 2)
+
+
 def quantize_ggml(w: torch.Tensor, type_name: str) -> GGMLQuantized:
-    """Quantize a [N, K] weight with ggml's reference Q4_0/Q8_0 quantizer."""
+    """Quantize a [N, K] weight with ggml's reference Q4_0/Q8_0 quantizer,
+    or with ops.quantize_kq's plain Q4_K/Q6_K quantizer."""
     from helix_amd import ops
+    if type_name in _KQ_FMT:
+        fmt = _KQ_FMT[type_name]
+        return GGMLQuantized(ops.pack_ggml_kq(ops.quantize_kq(w, fmt), fmt),
+                             tuple(w.shape), type_name)
     fmt = _WQ_FMT[type_name]
     qs, d = ops.quantize_wq(w, fmt)
     return GGMLQuantized(ops.pack_ggml(qs, d, fmt), tuple(w.shape), type_name)
@@ -212,9 +240,50 @@ def _dequantize(raw: bytes, info: GGUFTensorInfo) -> torch.Tensor:
         hi = (qs >> 4).astype(np.float32) - 8.0
         out = np.concatenate([lo, hi], axis=1) * d
         return torch.from_numpy(out.reshape(-1))
+    if tname in ("Q4_K", "Q5_K"):
+        # super-block of 256 = d, dmin (f16), scales[12] (eight 6-bit
+        # scale/min pairs), [Q5_K: qh[32], the fifth bits], qs[128];
+        # x = (d*sc_j) * q - dmin*m_j per 32-element sub-block j
+        bsz = 144 if tname == "Q4_K" else 176
+        blk = np.frombuffer(raw, dtype=np.uint8).reshape(-1, bsz)
+        d = blk[:, 0:2].copy().view("<f2").astype(np.float32)       # [B, 1]
+        dmin = blk[:, 2:4].copy().view("<f2").astype(np.float32)
+        s = blk[:, 4:16]
+        sc = np.concatenate(
+            [s[:, 0:4] & 63, (s[:, 8:12] & 0xF) | ((s[:, 0:4] >> 6) << 4)], 1)
+        m = np.concatenate(
+            [s[:, 4:8] & 63, (s[:, 8:12] >> 4) | ((s[:, 4:8] >> 6) << 4)], 1)
+        qs = blk[:, bsz - 128:].reshape(-1, 4, 1, 32)
+        # bytes 32c..32c+31: low nibbles are sub-block 2c, high 2c+1
+        q = np.concatenate([qs & 0x0F, qs >> 4], axis=2).reshape(-1, 8, 32)
+        if tname == "Q5_K":
+            qh = blk[:, 16:48].reshape(-1, 1, 32)
+            bit = (qh >> np.arange(8, dtype=np.uint8).reshape(1, 8, 1)) & 1
+            q = q + (bit << 4)
+        ds = (d * sc.astype(np.float32))[:, :, None]
+        dm = (dmin * m.astype(np.float32))[:, :, None]
+        out = ds * q.astype(np.float32) - dm
+        return torch.from_numpy(out.reshape(-1))
+    if tname == "Q6_K":
+        # super-block of 256 = ql[128], qh[64], scales[16] (int8), d (f16);
+        # element 128h + 32g + l: low 4 bits from ql[64h + 32(g&1) + l]
+        # (low nibble for g < 2), high 2 from (qh[32h + l] >> 2g) & 3;
+        # x = (d * scales[8h + 2g + l/16]) * (q - 32)
+        blk = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 210)
+        ql = blk[:, :128].reshape(-1, 2, 2, 32)
+        low = np.concatenate([ql & 0x0F, ql >> 4], axis=2)          # h, g, l
+        qh = blk[:, 128:192].reshape(-1, 2, 1, 32)
+        sh = (2 * np.arange(4, dtype=np.uint8)).reshape(1, 1, 4, 1)
+        high = (qh >> sh) & 3
+        q = (low | (high << 4)).astype(np.int32) - 32
+        sc = blk[:, 192:208].copy().view(np.int8).astype(np.float32)
+        d = blk[:, 208:210].copy().view("<f2").astype(np.float32)
+        ds = (d * sc).reshape(-1, 2, 4, 2, 1)
+        out = ds * q.reshape(-1, 2, 4, 2, 16).astype(np.float32)
+        return torch.from_numpy(out.reshape(-1))
     raise NotImplementedError(
-        f"dequantize {tname}: only F32/F16/BF16/Q8_0/Q4_0 supported "
-        f"(estimation supports all types)")
+        f"dequantize {tname}: only F32/F16/BF16/Q8_0/Q4_0/Q4_K/Q5_K/Q6_K "
+        f"supported (estimation supports all types)")
 
 
 # -- llama.cpp -> helix_amd name mapping -------------------------------
@@ -384,10 +453,13 @@ _FUSED_PARTS = {
 
 def _install_resident(model, g: GGUFFile) -> set:
     """Install every projection whose GGUF parts are all the same one of
-    Q4_0/Q8_0 as a WQLinear holding the file's blocks. Returns the GGUF
-    tensor names consumed."""
+    Q4_0/Q8_0 as a WQLinear, and every projection whose parts are each
+    Q4_K or Q6_K (not necessarily the same) as a KQLinear with one segment
+    per part, holding the file's blocks. Any other mix stays dense.
+    Returns the GGUF tensor names consumed."""
     from helix_amd import ops
-    from helix_amd.models.quant import WQLinear, attach_wq_scratch
+    from helix_amd.models.quant import (KQLinear, WQLinear,
+                                        attach_wq_scratch)
     cfg = model.cfg
     todo = []
     for i in range(cfg.num_layers):
@@ -395,8 +467,12 @@ def _install_resident(model, g: GGUFFile) -> set:
             names = [f"blk.{i}.{p}.weight" for p, _ in parts]
             if not all(n in g.tensors for n in names):
                 continue
-            types = {g.tensors[n].type_name for n in names}
-            if len(types) != 1 or next(iter(types)) not in _WQ_FMT:
+            types = [g.tensors[n].type_name for n in names]
+            if len(set(types)) == 1 and types[0] in _WQ_FMT:
+                fmts, block = [_WQ_FMT[types[0]]] * len(names), 32
+            elif all(t in _KQ_FMT for t in types):
+                fmts, block = [_KQ_FMT[t] for t in types], 256
+            else:
                 continue
             owner = model.get_submodule(f"layers.{i}.{proj.split('.')[0]}")
             lin = getattr(owner, proj.split(".")[1])
@@ -406,36 +482,45 @@ def _install_resident(model, g: GGUFFile) -> set:
             if any(len(t.shape) != 2 or t.shape[1] != lin.in_features
                    for t in infos) or \
                     sum(t.shape[0] for t in infos) != lin.out_features or \
-                    lin.in_features % 32 or lin.out_features % 16:
+                    lin.in_features % block or lin.out_features % 16:
                 continue
-            todo.append((owner, proj.split(".")[1], lin, names, parts,
-                         _WQ_FMT[next(iter(types))]))
+            # a K-quant segment is a launch of its own: each part's rows
+            # must be whole 16-channel tiles
+            if block == 256 and any(t.shape[0] % 16 for t in infos):
+                continue
+            todo.append((owner, proj.split(".")[1], lin, names, parts, fmts))
     if not todo:
         return set()
     dev = todo[0][2].weight.device
     used = set()
-    for owner, attr, lin, names, parts, fmt in todo:
-        qs_parts, d_parts = [], []
-        for n, (_, role) in zip(names, parts):
-            qs, d = ops.unpack_ggml(g.read_raw(n), g.tensors[n].shape, fmt)
+    for owner, attr, lin, names, parts, fmts in todo:
+        kq = fmts[0] in _KQ_FMT.values()
+        plane_parts = []
+        for n, (_, role), fmt in zip(names, parts, fmts):
+            unpack = ops.unpack_ggml_kq if kq else ops.unpack_ggml
+            planes = unpack(g.read_raw(n), g.tensors[n].shape, fmt)
             # a block never crosses a row, so the Q/K row permutation
-            # applies to the planes as whole rows
-            if role == "q":
-                qs, d = (unpermute_rope(qs, cfg.num_heads),
-                         unpermute_rope(d, cfg.num_heads))
-            elif role == "k":
-                qs, d = (unpermute_rope(qs, cfg.num_kv_heads),
-                         unpermute_rope(d, cfg.num_kv_heads))
-            qs_parts.append(qs)
-            d_parts.append(d)
+            # applies to every plane as whole rows
+            heads = {"q": cfg.num_heads, "k": cfg.num_kv_heads}.get(role)
+            if heads is not None:
+                planes = tuple(
+                    unpermute_rope(p.reshape(p.shape[0], -1), heads)
+                    .reshape(p.shape) for p in planes)
+            plane_parts.append(planes)
             used.add(n)
         # the bias stays the model's own: map_gguf_name maps no bias tensor
-        # today; when it does, the loader must write WQLinear.bias, which
-        # is a buffer and not among named_parameters()
+        # today; when it does, the loader must write the module's bias,
+        # which is a buffer and not among named_parameters()
         bias = None if lin.bias is None else lin.bias.data
-        setattr(owner, attr, WQLinear(
-            torch.cat(qs_parts, dim=0).contiguous().to(dev),
-            torch.cat(d_parts, dim=0).contiguous().to(dev), fmt, bias))
+        if kq:
+            mod = KQLinear(
+                [(fmt, tuple(p.contiguous().to(dev) for p in planes))
+                 for fmt, planes in zip(fmts, plane_parts)], bias)
+        else:
+            qs, d = (torch.cat(ps, dim=0).contiguous().to(dev)
+                     for ps in zip(*plane_parts))
+            mod = WQLinear(qs, d, fmts[0], bias)
+        setattr(owner, attr, mod)
     attach_wq_scratch(model)
     return used
 
@@ -444,8 +529,9 @@ def _install_resident(model, g: GGUFFile) -> set:
 def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     """Load a GGUF llama checkpoint into a helix_amd Llama model
     (dequantizing to the model dtype; Q/K rope rows un-permuted). With
-    keep_quantized, Q4_0/Q8_0 projections stay resident as the file's
-    blocks (WQLinear); see the module docstring."""
+    keep_quantized, Q4_0/Q8_0 projections (WQLinear) and Q4_K/Q6_K
+    projections (KQLinear) stay resident as the file's blocks; see the
+    module docstring."""
     g = GGUFFile(path)
     resident = _install_resident(model, g) if keep_quantized else set()
     params = dict(model.named_parameters())

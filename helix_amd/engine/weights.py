@@ -109,8 +109,9 @@ def load_llama_weights(model, ckpt_dir: str, use_async: bool = True,
     model. On GPU, tensors are staged through a pinned-host buffer and
     copied on a side stream (hipMemcpyAsync) so decode streams on the
     default stream are not serialized behind weight traffic.
-    keep_quantized applies to GGUF checkpoints only: Q4_0/Q8_0 projections
-    stay resident as the file's blocks (engine/gguf.py)."""
+    keep_quantized applies to GGUF checkpoints only: Q4_0/Q8_0 and
+    Q4_K/Q6_K projections stay resident as the file's blocks
+    (engine/gguf.py)."""
     # GGUF checkpoints (llama.cpp ecosystem) route through the native
     # GGUF loader (engine/gguf.py): file path or a dir holding one.
     gguf_path = None

@@ -1,5 +1,6 @@
 """Weights-quantized serving: fp8 e4m3 W8A8 with per-channel/per-token
-scales, and weight-only ggml Q4_0/Q8_0 (second half of this file).
+scales, and weight-only ggml Q4_0/Q8_0 and Q4_K/Q6_K (second half of this
+file).
 
 The reference serves quantized checkpoints through vLLM/Ollama
 quantization support; here quantization is a
@@ -109,6 +110,10 @@ class WQLinear(nn.Module):
         bias = None if lin.bias is None else lin.bias.data
         return cls(qs, d, fmt, bias)
 
+    @property
+    def device(self):
+        return self.qs.device
+
     def _apply(self, fn, recurse=True):
         # model.to(dtype) / .half() / .bfloat16() convert every floating
         # buffer; the block scales are fp16 by format, so `d` follows the
@@ -132,21 +137,133 @@ class WQLinear(nn.Module):
         return out.reshape(*shape, self.out_features)
 
 
+# -- weight-only ggml K-quants, Q4_K / Q6_K (ops/hip/gemm_kq.hip) -------
+
+_KQ_PLANES = {"q4_k": ("qs", "hdr"), "q6_k": ("ql", "qh", "sc", "d")}
+
+
+class KQLinear(nn.Module):
+    """Drop-in nn.Linear replacement holding ggml K-quant planes. The rows
+    are an ordered list of segments, each of its own format: a fused
+    projection keeps the types its parts have in the file (a Q4_K_M file's
+    qkv_proj is q4_k, q4_k, q6_k). Segment i's planes are the buffers
+    `s{i}_{plane}` (ops/reference.py names the planes), `fmts[i]` its
+    format, `rows[i]` its first output row.
+
+    Up to ops.KQ_FUSED_MAX_M rows: one fused dequant GEMM launch per
+    segment, each writing its columns of one [M, N] output. Larger batches:
+    every segment dequantizes into its row range of `scratch`, then one
+    library GEMM over the whole weight. `scratch` follows WQLinear's
+    ownership rule (attach_wq_scratch): one buffer per model and GPU."""
+
+    def __init__(self, segments, bias: torch.Tensor | None = None,
+                 scratch: torch.Tensor | None = None):
+        super().__init__()
+        if not segments:
+            raise ValueError("KQLinear: no segments")
+        self.fmts, self.rows = [], []
+        n, K = 0, None
+        for i, (fmt, planes) in enumerate(segments):
+            ops.kq_check(fmt)
+            names = _KQ_PLANES[fmt]
+            if len(planes) != len(names):
+                raise ValueError(f"KQLinear: {fmt} takes {len(names)} planes")
+            sn, sk = ops.kq_shape(planes, fmt)
+            if K is not None and sk != K:
+                raise ValueError(f"KQLinear: segment {i} has K={sk}, not {K}")
+            if sk % 256 or sn % 16:
+                raise ValueError(f"KQLinear: segment {i} is [{sn}, {sk}]; "
+                                 f"need N % 16 == 0 and K % 256 == 0")
+            K = sk
+            for name, p in zip(names, planes):
+                self.register_buffer(f"s{i}_{name}", p.contiguous(),
+                                     persistent=True)
+            self.fmts.append(fmt)
+            self.rows.append(n)
+            n += sn
+        if bias is not None:
+            self.register_buffer("bias", bias.contiguous(), persistent=True)
+        else:
+            self.bias = None
+        self.out_features, self.in_features = n, K
+        self.scratch = scratch
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear, fmt: str) -> "KQLinear":
+        bias = None if lin.bias is None else lin.bias.data
+        return cls([(fmt, ops.quantize_kq(lin.weight.data, fmt))], bias)
+
+    def planes(self, i: int):
+        return tuple(getattr(self, f"s{i}_{name}")
+                     for name in _KQ_PLANES[self.fmts[i]])
+
+    @property
+    def segments(self):
+        return [(f, self.planes(i)) for i, f in enumerate(self.fmts)]
+
+    @property
+    def device(self):
+        return self.planes(0)[0].device
+
+    def _apply(self, fn, recurse=True):
+        # as WQLinear._apply: the fp16 super-block scales of q6_k are fp16 by
+        # format and follow the device only (the integer planes are never
+        # touched by a dtype cast)
+        keep = {f"s{i}_d": getattr(self, f"s{i}_d")
+                for i, f in enumerate(self.fmts) if f == "q6_k"}
+        super()._apply(fn, recurse)
+        for n, b in keep.items():
+            if self._buffers[n].dtype != torch.float16:
+                self._buffers[n] = b.to(self._buffers[n].device)
+        if self.scratch is not None and self.scratch.device != self.device:
+            self.scratch = None
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape[:-1]
+        x2 = x.reshape(-1, self.in_features)
+        if x2.is_cuda and not x2.is_contiguous():
+            x2 = x2.contiguous()
+        M, N, K = x2.shape[0], self.out_features, self.in_features
+        if not x2.is_cuda:
+            # the definition: F.linear on the dequantized fused weight
+            w = torch.cat([ops.dequantize_kq(p, f).to(x2.dtype)
+                           for f, p in self.segments], dim=0)
+            out = torch.nn.functional.linear(x2, w, self.bias)
+            return out.reshape(*shape, N)
+        if 0 < M <= ops.KQ_FUSED_MAX_M:
+            out = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+            for i, fmt in enumerate(self.fmts):
+                ops.gemm_kq(x2, self.planes(i), fmt, self.bias, out=out,
+                            col_off=self.rows[i])
+            return out.reshape(*shape, N)
+        if self.scratch is not None:
+            w = self.scratch.view(-1)[:N * K].view(N, K)
+        else:
+            w = torch.empty(N, K, dtype=torch.bfloat16, device=x2.device)
+        ends = self.rows[1:] + [N]
+        for i, fmt in enumerate(self.fmts):
+            ops.dequant_kq(self.planes(i), fmt, out=w[self.rows[i]:ends[i]])
+        out = torch.nn.functional.linear(x2, w, self.bias)
+        return out.reshape(*shape, N)
+
+
 def attach_wq_scratch(model: nn.Module) -> None:
     """Give `model` its own dequant buffer: one bf16 tensor per GPU it has
-    WQLinears on, sized for the largest of them and shared by them alone.
+    WQLinears or KQLinears on, sized for the largest of them and shared by
+    them alone.
     Called when the weights are installed and again by the engine if the
     model was moved since; never from a forward. A model whose modules
     already hold a fitting buffer is left as it is (captured graphs point
     into it)."""
     mods = [m for m in model.modules()
-            if isinstance(m, WQLinear) and m.qs.is_cuda]
+            if isinstance(m, (WQLinear, KQLinear)) and m.device.type == "cuda"]
     need: dict = {}
     for m in mods:
         n = m.in_features * m.out_features
-        need[m.qs.device] = max(need.get(m.qs.device, 0), n)
+        need[m.device] = max(need.get(m.device, 0), n)
     for dev, numel in need.items():
-        mine = [m for m in mods if m.qs.device == dev]
+        mine = [m for m in mods if m.device == dev]
         cur = mine[0].scratch
         if cur is not None and cur.device == dev and cur.numel() >= numel \
                 and all(m.scratch is cur for m in mine):
@@ -160,8 +277,14 @@ def quantize_model_wq(model: nn.Module, fmt: str,
                       skip: tuple = ("lm_head",)) -> int:
     """Swap eligible Linears (in_features % 32 == 0, out_features % 16 == 0,
     name outside `skip`; a bias is kept) for WQLinear, then give the model
-    its dequant scratch. Returns the number of modules converted."""
-    ops.wq_bits(fmt)
+    its dequant scratch. With a K-quant format ("q4_k", "q6_k") the block
+    is 256 (in_features % 256 == 0) and the module a single-segment
+    KQLinear. Returns the number of modules converted."""
+    kq = fmt in ops.KQ_FORMATS
+    if not kq:
+        ops.wq_bits(fmt)
+    block = 256 if kq else 32
+    cls = KQLinear if kq else WQLinear
     converted = 0
     for name, mod in list(model.named_modules()):
         for child_name, child in list(mod.named_children()):
@@ -170,13 +293,13 @@ def quantize_model_wq(model: nn.Module, fmt: str,
                 continue
             if any(s in full for s in skip):
                 continue
-            if child.in_features % 32 != 0 or child.out_features % 16 != 0:
+            if child.in_features % block != 0 or child.out_features % 16 != 0:
                 continue
-            setattr(mod, child_name, WQLinear.from_linear(child, fmt))
+            setattr(mod, child_name, cls.from_linear(child, fmt))
             converted += 1
     attach_wq_scratch(model)
     return converted
 
 
 def has_wq(model: nn.Module) -> bool:
-    return any(isinstance(m, WQLinear) for m in model.modules())
+    return any(isinstance(m, (WQLinear, KQLinear)) for m in model.modules())

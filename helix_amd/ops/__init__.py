@@ -400,6 +400,93 @@ def gemm_wq(x: torch.Tensor, qs: torch.Tensor, d: torch.Tensor, fmt: str,
     return torch.nn.functional.linear(x, w, bias)
 
 
+# -- ggml Q4_K / Q6_K weight-only GEMM (ops/hip/gemm_kq.hip) ------------
+from .reference import (quantize_kq, dequantize_kq, pack_ggml_kq,  # noqa: E402,F401
+                        unpack_ggml_kq, kq_check, kq_shape, KQ_FORMATS,
+                        KQ_BLOCK_BYTES)
+
+# Largest M the fused K-quant kernel serves; the same rule as
+# WQ_FUSED_MAX_M: a member of graph_runner.BATCH_BUCKETS, not above the
+# kernel's own limit (_C.KQ_KERNEL_MAX_M = 32), at which the kernel still
+# beats the bf16 library GEMM for both formats at all four llama3-8b
+# projection shapes (profiles/r06_kquant.md, two runs: q4_k 1.15-2.68x and
+# q6_k 1.01-2.31x at M = 16; 0.64-1.56x at M = 32, three of four shapes
+# losing).
+KQ_FUSED_MAX_M = 16
+
+
+def kq_waves(N: int, K: int) -> int:
+    """K-split factor (waves per workgroup) the fused kernel uses for a
+    [N, K] weight: the host's own function, a property of the shape."""
+    return int(_native().kq_waves(N, K))
+
+
+def dequant_kq(planes, fmt: str,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Planes -> bf16 [N, K]. GPU: the HIP kernel, into `out` when given
+    (any contiguous bf16 buffer of at least N*K elements). CPU: the torch
+    reference, `out` unused."""
+    kq_check(fmt)
+    if not planes[0].is_cuda:
+        return dequantize_kq(planes, fmt, torch.bfloat16)
+    N, K = kq_shape(planes, fmt)
+    if out is None:
+        w = torch.empty(N, K, dtype=torch.bfloat16, device=planes[0].device)
+    else:
+        if out.dtype != torch.bfloat16 or out.numel() < N * K \
+                or not out.is_contiguous():
+            raise ValueError(
+                f"dequant_kq: scratch must be contiguous bf16 with at least "
+                f"{N * K} elements, got {out.dtype} x {out.numel()}")
+        w = out.view(-1)[:N * K].view(N, K)
+    _native().dequant_kq(w, list(planes), fmt)
+    return w
+
+
+def gemm_kq(x: torch.Tensor, planes, fmt: str,
+            bias: torch.Tensor | None = None,
+            scratch: torch.Tensor | None = None,
+            out: torch.Tensor | None = None,
+            col_off: int = 0) -> torch.Tensor:
+    """out[:, col_off:col_off+N] = x[M,K] @ dequant(planes)^T
+    (+ bias[col_off:col_off+N]): ggml Q4_K/Q6_K weights kept quantized.
+    `out` is a bf16 [M, ldo] buffer shared by the segments of a fused
+    projection (allocated [M, N] when None, with col_off = 0); `bias`
+    is indexed like `out`'s columns. Returns `out`.
+    GPU, M <= KQ_FUSED_MAX_M: dequant fused into the MFMA loop. GPU, larger
+    M: dequant_kq into `scratch` (allocated per call when None) + the
+    library GEMM. CPU: F.linear on the dequantized weight, the definition
+    tests hold the rest of the stack to."""
+    kq_check(fmt)
+    N, K = kq_shape(planes, fmt)
+    if x.dim() != 2:
+        raise ValueError(f"gemm_kq: x must be [M, K], got {tuple(x.shape)}")
+    M = x.shape[0]
+    if out is None:
+        if col_off:
+            raise ValueError("gemm_kq: col_off needs an `out` buffer")
+    elif out.dim() != 2 or out.shape[0] != M or out.shape[1] < col_off + N:
+        raise ValueError(f"gemm_kq: out is {tuple(out.shape)}, need "
+                         f"[{M}, >= {col_off + N}]")
+    seg_bias = None if bias is None else bias[col_off:col_off + N]
+    if x.is_cuda and 0 < M <= KQ_FUSED_MAX_M:
+        if out is None:
+            out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+        _native().gemm_kq(out, col_off, x, list(planes), bias, fmt)
+        return out
+    if not x.is_cuda:
+        w = dequantize_kq(planes, fmt, torch.float32).to(x.dtype)
+    elif x.dtype != torch.bfloat16:
+        raise ValueError(f"gemm_kq: x must be bf16 on GPU, got {x.dtype}")
+    else:
+        w = dequant_kq(planes, fmt, out=scratch)
+    y = torch.nn.functional.linear(x, w, seg_bias)
+    if out is None:
+        return y
+    out[:, col_off:col_off + N] = y
+    return out
+
+
 def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)

@@ -64,6 +64,13 @@ void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
 void dequant_wq(torch::Tensor out, torch::Tensor qs, torch::Tensor d,
                 int64_t bits);
 int64_t wq_kernel_max_m();
+void gemm_kq(torch::Tensor out, int64_t col_off, torch::Tensor x,
+             std::vector<torch::Tensor> planes,
+             c10::optional<torch::Tensor> bias, std::string fmt);
+void dequant_kq(torch::Tensor out, std::vector<torch::Tensor> planes,
+                std::string fmt);
+int64_t kq_kernel_max_m();
+int64_t kq_waves(int64_t N, int64_t K);
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b);
 torch::Tensor ar_create(int64_t world, int64_t rank, int64_t capacity);
 void ar_open(std::vector<torch::Tensor> handles);
@@ -108,6 +115,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_wq", &dequant_wq,
         "Q4_0/Q8_0 planes -> bf16 [N,K] into a caller buffer");
   m.attr("WQ_KERNEL_MAX_M") = wq_kernel_max_m();
+  m.def("gemm_kq", &gemm_kq,
+        "Q4_K/Q6_K weight-only GEMM into out[:, col_off:col_off+N], dequant "
+        "fused into the MFMA loop (M <= 32)");
+  m.def("dequant_kq", &dequant_kq,
+        "Q4_K/Q6_K planes -> bf16 [N,K] into a caller buffer");
+  m.def("kq_waves", &kq_waves,
+        "K-split factor (waves per workgroup) gemm_kq uses for a [N,K] weight");
+  m.attr("KQ_KERNEL_MAX_M") = kq_kernel_max_m();
   m.def("mfma_probe", &mfma_probe, "16x16x32 MFMA layout probe");
   m.def("ar_create", &ar_create,
         "Allocate one-shot allreduce mailbox; returns IPC handle bytes");

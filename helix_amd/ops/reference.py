@@ -334,3 +334,174 @@ def unpack_ggml(raw, shape, fmt: str):
     if bits == 8:
         qs = qs.view(torch.int8)
     return qs, d
+
+
+# -- ggml K-quant weight-only formats: Q4_K / Q6_K ----------------------
+# Super-blocks of 256 consecutive elements along K. Device layout is the
+# block's fields as planes, byte for byte as in the file (unpack is a
+# strided copy, pack its exact inverse; scales are NOT pre-multiplied into a
+# wider plane, which would cost a third more weight bytes):
+#   q4_k: (qs  uint8 [N, K/2],          128 nibble bytes per super-block
+#          hdr uint8 [N, K/256, 16])    d fp16, dmin fp16, scales[12]
+#   q6_k: (ql  uint8 [N, K/2], qh uint8 [N, K/4], sc int8 [N, K/16],
+#          d   fp16  [N, K/256])
+# docs/KERNELS.md has the bit layout. No file written by llama.cpp has been
+# read with this code yet.
+
+KQ_BLOCK = 256
+KQ_FORMATS = {"q4_k", "q6_k"}
+KQ_BLOCK_BYTES = {"q4_k": 144, "q6_k": 210}
+
+
+def kq_check(fmt: str) -> str:
+    if fmt not in KQ_FORMATS:
+        raise ValueError(f"unknown K-quant format {fmt!r} "
+                         f"(expected one of {sorted(KQ_FORMATS)})")
+    return fmt
+
+
+def kq_shape(planes, fmt: str):
+    """(N, K) of a plane tuple."""
+    kq_check(fmt)
+    return planes[0].shape[0], planes[0].shape[1] * 2
+
+
+def _q4k_scale_min(hdr: torch.Tensor):
+    """hdr [..., 16] uint8 -> (d*sc, dmin*m), each fp32 [..., 8]."""
+    d = hdr[..., 0:2].contiguous().view(torch.float16).float()      # [..., 1]
+    dmin = hdr[..., 2:4].contiguous().view(torch.float16).float()
+    s = hdr[..., 4:16].to(torch.int32)
+    sc = torch.cat([s[..., 0:4] & 63,
+                    (s[..., 8:12] & 0xF) | ((s[..., 0:4] >> 6) << 4)], -1)
+    m = torch.cat([s[..., 4:8] & 63,
+                   (s[..., 8:12] >> 4) | ((s[..., 4:8] >> 6) << 4)], -1)
+    return d * sc.float(), dmin * m.float()
+
+
+def dequantize_kq(planes, fmt: str,
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planes -> [N, K]. Q4_K: (d*sc)*nib - dmin*m, Q6_K: (d*sc)*q, in fp32
+    in that order (one fp32 rounding each), then one rounding to `dtype`."""
+    kq_check(fmt)
+    N, K = kq_shape(planes, fmt)
+    nb = K // KQ_BLOCK
+    if fmt == "q4_k":
+        qs, hdr = planes
+        ds, dm = _q4k_scale_min(hdr)                          # [N, nb, 8]
+        b = qs.reshape(N, nb, 4, 1, 32)
+        # bytes 32c..32c+31: low nibbles are sub-block 2c, high 2c+1
+        nib = torch.cat([b & 0x0F, b >> 4], dim=3).reshape(N, nb, 8, 32)
+        y = ds[..., None] * nib.float() - dm[..., None]
+    else:
+        ql, qh, sc, d = planes
+        b = ql.reshape(N, nb, 2, 2, 32)                       # half, g&1, l
+        low = torch.cat([b & 0x0F, b >> 4], dim=3)            # half, g, l
+        h = qh.reshape(N, nb, 2, 1, 32)
+        shift = torch.tensor([0, 2, 4, 6], dtype=torch.uint8).view(4, 1)
+        high = (h >> shift) & 3
+        q = (low | (high << 4)).to(torch.int32) - 32          # [N,nb,2,4,32]
+        s = d.float().reshape(N, nb, 1) * sc.reshape(N, nb, 16).float()
+        s = s.reshape(N, nb, 2, 4, 2, 1)                      # 8h + 2g + l/16
+        y = s * q.reshape(N, nb, 2, 4, 2, 16).float()
+    return y.reshape(N, K).to(dtype)
+
+
+def _nearest(v: torch.Tensor) -> torch.Tensor:
+    return torch.floor(v + 0.5)
+
+
+def _safe_div(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    return torch.where(b != 0, a / torch.where(b != 0, b, torch.ones_like(b)),
+                       torch.zeros_like(a))
+
+
+def quantize_kq(w: torch.Tensor, fmt: str):
+    """A plain deterministic K-quant quantizer, NOT ggml's search quantizer
+    (make_qkx2_quants / make_qx_quants): it only has to write valid blocks.
+    w [N, K] -> planes.
+
+    Q4_K, per 32-element sub-block: m = max(0, -min), s = (max + m) / 15;
+    per super-block d = max_j s / 63 and dmin = max_j m / 63, stored as fp16;
+    the 6-bit codes and the nibbles are rounded to nearest and clamped.
+    Q6_K: the per-16 scale is the signed value of largest magnitude over
+    -32, d = max |scale| / 127 as fp16, int8 scale codes and q rounded to
+    nearest, q clamped to [-32, 31]. All-zero blocks give all-zero fields."""
+    kq_check(fmt)
+    if w.dim() != 2 or w.shape[1] % KQ_BLOCK:
+        raise ValueError(f"quantize_kq: need [N, K] with K % 256 == 0, "
+                         f"got {tuple(w.shape)}")
+    N, K = w.shape
+    nb = K // KQ_BLOCK
+    if fmt == "q4_k":
+        x = w.detach().float().reshape(N, nb, 8, 32)
+        m = x.amin(-1).clamp_(max=0).abs_()                    # [N, nb, 8]
+        s = (x.amax(-1) + m) / 15.0
+        d = (s.amax(-1, keepdim=True) / 63.0).to(torch.float16)
+        dmin = (m.amax(-1, keepdim=True) / 63.0).to(torch.float16)
+        sc = _nearest(_safe_div(s, d.float())).clamp_(0, 63)
+        mc = _nearest(_safe_div(m, dmin.float())).clamp_(0, 63)
+        ds, dm = d.float() * sc, dmin.float() * mc             # as decoded
+        nib = _nearest(_safe_div(x + dm[..., None], ds[..., None]))
+        nib = nib.clamp_(0, 15).to(torch.uint8).reshape(N, nb, 4, 2, 32)
+        qs = (nib[..., 0, :] | (nib[..., 1, :] << 4)).reshape(N, K // 2)
+        sc, mc = sc.to(torch.uint8), mc.to(torch.uint8)
+        scales = torch.cat([
+            sc[..., :4] | ((sc[..., 4:] >> 4) << 6),
+            mc[..., :4] | ((mc[..., 4:] >> 4) << 6),
+            (sc[..., 4:] & 0xF) | ((mc[..., 4:] & 0xF) << 4)], -1)
+        hdr = torch.cat([d.view(torch.uint8), dmin.view(torch.uint8), scales],
+                        -1)
+        return qs.contiguous(), hdr.contiguous()
+    x = w.detach().float().reshape(N, nb, 16, 16)
+    idx = x.abs().argmax(dim=-1, keepdim=True)
+    s = x.gather(-1, idx).squeeze(-1) / -32.0                  # [N, nb, 16]
+    d = (s.abs().amax(-1, keepdim=True) / 127.0).to(torch.float16)
+    sc = _nearest(_safe_div(s, d.float())).clamp_(-128, 127)
+    ds = d.float() * sc
+    q = _nearest(_safe_div(x, ds[..., None])).clamp_(-32, 31)
+    u = (q + 32).to(torch.uint8).reshape(N, nb, 2, 4, 32)      # half, g, l
+    lo4, hi2 = u & 0x0F, u >> 4
+    ql = (lo4[..., :2, :] | (lo4[..., 2:, :] << 4)).reshape(N, K // 2)
+    qh = (hi2[..., 0, :] | (hi2[..., 1, :] << 2) | (hi2[..., 2, :] << 4)
+          | (hi2[..., 3, :] << 6)).reshape(N, K // 4)
+    return (ql.contiguous(), qh.contiguous(),
+            sc.to(torch.int8).reshape(N, K // 16).contiguous(),
+            d.reshape(N, nb).contiguous())
+
+
+def pack_ggml_kq(planes, fmt: str) -> bytes:
+    """Planes -> ggml super-block bytes (block_q4_K: d, dmin, scales[12],
+    qs[128]; block_q6_K: ql[128], qh[64], scales[16], d)."""
+    kq_check(fmt)
+    N, K = kq_shape(planes, fmt)
+    nb = K // KQ_BLOCK
+    ps = [p.detach().cpu().contiguous() for p in planes]
+    if fmt == "q4_k":
+        parts = [ps[1].reshape(N, nb, 16), ps[0].reshape(N, nb, 128)]
+    else:
+        parts = [ps[0].reshape(N, nb, 128), ps[1].reshape(N, nb, 64),
+                 ps[2].view(torch.uint8).reshape(N, nb, 16),
+                 ps[3].view(torch.uint8).reshape(N, nb, 2)]
+    return torch.cat(parts, dim=-1).contiguous().numpy().tobytes()
+
+
+def unpack_ggml_kq(raw, shape, fmt: str):
+    """ggml super-block bytes of a [N, K] tensor -> planes: a strided copy,
+    no re-encoding."""
+    kq_check(fmt)
+    N, K = shape
+    if K % KQ_BLOCK:
+        raise ValueError(f"unpack_ggml_kq: K={K} is not a multiple of 256")
+    nb, bsz = K // KQ_BLOCK, KQ_BLOCK_BYTES[fmt]
+    buf = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+    if buf.numel() != N * nb * bsz:
+        raise ValueError(f"unpack_ggml_kq: {buf.numel()} bytes for shape "
+                         f"{tuple(shape)} {fmt}, expected {N * nb * bsz}")
+    b = buf.reshape(N, nb, bsz)
+    if fmt == "q4_k":
+        return (b[..., 16:].contiguous().reshape(N, K // 2),
+                b[..., :16].contiguous())
+    return (b[..., :128].contiguous().reshape(N, K // 2),
+            b[..., 128:192].contiguous().reshape(N, K // 4),
+            b[..., 192:208].contiguous().view(torch.int8).reshape(N, K // 16),
+            b[..., 208:210].contiguous().view(torch.float16).reshape(N, nb))

@@ -39,7 +39,8 @@ class ModelSpec:
     kv_cache_blocks: Optional[int] = None
     kv_memory_fraction: float = 0.30   # of total HBM, for auto-sizing
     tp: int = 1                        # tensor-parallel degree (xGMI group)
-    # None | "fp8" (W8A8) | "q4_0" | "q8_0" (ggml weight-only)
+    # None | "fp8" (W8A8) | "q4_0" | "q8_0" | "q4_k" | "q6_k" (ggml
+    # weight-only)
     quantization: Optional[str] = None
     kv_cache_dtype: str = "bf16"
     max_loras: int = 0                 # LoRA adapter slots (0 = off)
@@ -100,11 +101,13 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
     per_layer = (cfg.hidden_size * (cfg.q_size + 2 * cfg.kv_size)  # qkv
                  + cfg.q_size * cfg.hidden_size                     # o
                  + 3 * cfg.hidden_size * cfg.intermediate_size)     # mlp
-    # projection bytes per 32 weights: bf16 64, fp8 32, ggml blocks 34 / 18
-    # (embeddings/lm_head stay bf16)
-    blk_bytes = {"fp8": 32, "q8_0": 34, "q4_0": 18}.get(spec.quantization, 64)
-    weights = 2 * emb + blk_bytes * (cfg.num_layers * per_layer) // 32
-    if spec.quantization in ("q8_0", "q4_0"):
+    # projection bytes per 256 weights: bf16 512, fp8 256, ggml blocks
+    # 8 x 34 / 8 x 18, K-quant super-blocks 144 / 210 (embeddings/lm_head
+    # stay bf16)
+    blk_bytes = {"fp8": 256, "q8_0": 272, "q4_0": 144, "q4_k": 144,
+                 "q6_k": 210}.get(spec.quantization, 512)
+    weights = 2 * emb + blk_bytes * (cfg.num_layers * per_layer) // 256
+    if spec.quantization in ("q8_0", "q4_0", "q4_k", "q6_k"):
         # the model's bf16 dequant scratch for batches above the fused
         # kernel's cutoff: one buffer the size of its largest projection
         weights += 2 * max(cfg.hidden_size * (cfg.q_size + 2 * cfg.kv_size),

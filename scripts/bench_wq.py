@@ -1,7 +1,9 @@
 #!/usr/bin/env python
-"""Projection-GEMM benchmark for Q4_0/Q8_0 weight-only serving.
+"""Projection-GEMM benchmark for Q4_0/Q8_0 and Q4_K/Q6_K weight-only
+serving.
 
-Times ops.gemm_wq (both formats) against torch.nn.functional.linear on
+Times ops.gemm_wq and ops.gemm_kq (every format, or those given with
+--variant) against torch.nn.functional.linear on
 bf16 weights (the dense path, the baseline) at the llama3-8b projection
 shapes and decode/prefill batch sizes, and prints one JSON line per
 (shape, M, variant): median and min microseconds per call and the weight
@@ -35,8 +37,19 @@ MS = [1, 4, 16, 64, 128, 512]
 CACHE_BYTES = 768 << 20       # rotate over at least this many weight bytes
 
 
+VARIANTS = ("bf16", "q8_0", "q4_0", "q4_k", "q6_k")
+# bytes per 256 weights: bf16, 8 ggml blocks of 34 / 18, one super-block
+BYTES_PER_256 = {"bf16": 512, "q8_0": 272, "q4_0": 144, "q4_k": 144,
+                 "q6_k": 210}
+
+
 def weight_bytes(variant: str, N: int, K: int) -> int:
-    return N * K * {"bf16": 64, "q8_0": 34, "q4_0": 18}[variant] // 32
+    return N * K * BYTES_PER_256[variant] // 256
+
+
+def fused_max_m(variant: str) -> int:
+    return ops.KQ_FUSED_MAX_M if variant in ops.KQ_FORMATS \
+        else ops.WQ_FUSED_MAX_M
 
 
 def main():
@@ -44,6 +57,13 @@ def main():
     ap.add_argument("--shape", action="append",
                     help="NxK, repeatable (default: the llama3-8b set)")
     ap.add_argument("--m", type=int, action="append")
+    ap.add_argument("--variant", action="append", choices=VARIANTS[1:],
+                    help="repeatable (default: all); bf16, the baseline, "
+                    "is always timed")
+    ap.add_argument("--fused-max-m", type=int, default=0,
+                    help="time the fused kernels up to this M instead of "
+                    "the shipped cutoffs (to measure where the cutoff "
+                    "belongs)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -51,6 +71,9 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_wq.py needs a GPU")
     assert ops.have_native(), "native extension is not built"
+    if args.fused_max_m:
+        ops.WQ_FUSED_MAX_M = min(args.fused_max_m, ops._C.WQ_KERNEL_MAX_M)
+        ops.KQ_FUSED_MAX_M = min(args.fused_max_m, ops._C.KQ_KERNEL_MAX_M)
     dev = torch.device("cuda:0")
     lines = []
     for shape in args.shape or SHAPES:
@@ -58,11 +81,15 @@ def main():
         g = torch.Generator(device=dev).manual_seed(N + K)
         w = torch.randn(N, K, generator=g, device=dev) * 0.02
         variants = {}
-        for v in ("bf16", "q8_0", "q4_0"):
+        for v in ["bf16"] + list(args.variant or VARIANTS[1:]):
             copies = max(2, -(-CACHE_BYTES // weight_bytes(v, N, K)))
             if v == "bf16":
                 wb = w.to(torch.bfloat16)
                 variants[v] = [(wb.clone(),) for _ in range(copies)]
+            elif v in ops.KQ_FORMATS:
+                planes = ops.quantize_kq(w, v)
+                variants[v] = [tuple(p.clone() for p in planes)
+                               for _ in range(copies)]
             else:
                 qs, d = ops.quantize_wq(w, v)
                 variants[v] = [(qs.clone(), d.clone()) for _ in range(copies)]
@@ -73,6 +100,8 @@ def main():
             ws = variants[v][i % len(variants[v])]
             if v == "bf16":
                 return torch.nn.functional.linear(x, ws[0])
+            if v in ops.KQ_FORMATS:
+                return ops.gemm_kq(x, ws, v, scratch=scratch)
             return ops.gemm_wq(x, ws[0], ws[1], v, scratch=scratch)
 
         for M in args.m or MS:
@@ -96,7 +125,7 @@ def main():
                 med, mn = statistics.median(ts), min(ts)
                 rec = {"N": N, "K": K, "M": M, "variant": v,
                        "path": ("library" if v == "bf16" else
-                                "fused" if M <= ops.WQ_FUSED_MAX_M
+                                "fused" if M <= fused_max_m(v)
                                 else "dequant+library"),
                        "us_median": round(med, 2), "us_min": round(mn, 2),
                        "weight_bytes": weight_bytes(v, N, K),
