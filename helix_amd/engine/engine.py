@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from helix_amd import ops
-from helix_amd.engine.kv_cache import KVCache, chain_hash
+from helix_amd.engine.kv_cache import KVCache, chain_hash, check_block_size
 from helix_amd.engine.sampling_params import SamplingParams
 from helix_amd.models.llama import (DecodeMeta, LlamaConfig, LlamaForCausalLM,
                                     PrefillMeta, PRESETS)
@@ -78,6 +78,9 @@ class EngineConfig:
     kv_cache_dtype: str = "bf16"              # "bf16" | "fp8" (e4m3 KV)
     max_loras: int = 0                        # adapter slots (0 = LoRA off)
     max_lora_rank: int = 16
+
+    def __post_init__(self):
+        check_block_size(self.block_size)
 
 
 class LLMEngine:

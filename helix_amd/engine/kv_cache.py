@@ -105,13 +105,27 @@ class BlockAllocator:
         return None
 
 
+MIN_BLOCK_SIZE = 8
+
+
+def check_block_size(block_size: int) -> int:
+    """The decode kernel addresses a token with shift and mask and keeps
+    at most 128 / 8 + 1 block ids per chunk: the block size is a power of
+    two and at least MIN_BLOCK_SIZE."""
+    if block_size < MIN_BLOCK_SIZE or block_size & (block_size - 1):
+        raise ValueError(
+            f"block_size must be a power of two and at least "
+            f"{MIN_BLOCK_SIZE}, got {block_size}")
+    return block_size
+
+
 class KVCache:
     """Per-model paged KV storage: one (K, V) pair of
     [num_blocks, Hkv, block_size, head_dim] bf16 tensors per layer."""
 
     def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int,
                  block_size: int, num_blocks: int, device, dtype=torch.bfloat16):
-        self.block_size = block_size
+        self.block_size = check_block_size(block_size)
         self.num_blocks = num_blocks
         self.caches = []
         for _ in range(num_layers):

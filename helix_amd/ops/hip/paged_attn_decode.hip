@@ -19,6 +19,10 @@
 //      B: per-head online softmax (running m, l), one wave per head.
 //      C: V accumulation, thread owns 8 dims, VPS-token load batches
 //         (bf16 rows staged raw, fp8 rows converted as they land).
+//  - No K or V address waits on a block-table load: the physical ids
+//    of the blocks a chunk touches (at most 128 / bs + 1) are staged in
+//    LDS two chunks ahead (blk_ids below); a token's address is a
+//    ds_read, a shift and a mask (block_size is a power of two >= 8).
 //  - KV8: the paged cache holds OCP e4m3 bytes (opt-in
 //    kv_cache_dtype="fp8"): halves the KV traffic this kernel is
 //    latency/BW-bound on; dequant is one v_cvt per element.
@@ -34,7 +38,11 @@
 //  - waves/SIMD floor of 2 without K prefetch: +-0, same file.
 //  - V prefetch across chunks: 202 VGPRs, occupancy 3 -> 2, -7 % e2e,
 //    same file.
+//  - First V batch of a chunk issued ahead of the K prefetch (consumed
+//    at vmcnt(16) with the K rows in flight): 192 VGPRs, occupancy
+//    3 -> 2, +5 % time at B=512, profiles/r07_decode_blockids.md.
 #include "common.h"
+#include <type_traits>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -48,6 +56,10 @@ constexpr int MAX_G = 8;
 constexpr int PART_QUANT = 128;   // split-K partition sizes are multiples
 constexpr int MAX_PARTS = 512;    // weights the reduce kernel holds in LDS
 constexpr int TARGET_WGS = 1024;  // split-K until the grid is this large
+constexpr int MIN_BS = 8;         // smallest cache block the host lets in
+// Block ids one chunk can touch: CHUNK / bs, plus one because a window
+// starts the chunks off the block grid.
+constexpr int IDS_MAX = CHUNK / MIN_BS + 1;
 
 // How a cache of each type is read: 16-byte K-row vectors, 8-element
 // V vectors, and the widen to fp32.
@@ -75,8 +87,16 @@ template <> struct CacheElem<true> {
 // more V bytes are in flight per wave before any conversion VALU
 // touches them: 4 on a full grid, 8 when the grid underfills the chip
 // (see launch_decode). fp8 does not stage raw and is built with 4 only.
+//
+// Waves/SIMD floor (second launch bound): 2 gives the register room for
+// the 16-deep K prefetch at D = 128 bf16. The kernels whose K row is 32
+// registers or fewer and that serve at most two heads fit 128 VGPRs, as
+// they always did; the floor of 4 keeps them there (at a floor of 2 the
+// scheduler takes 129-132 and loses a wave: +9 % time at D = 64, G = 2).
 template <int DHEAD, int G, bool KV8, int VPS>
-__global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
+__global__ __launch_bounds__(NTHREADS,
+                             (G <= 2 && (DHEAD == 64 || KV8)) ? 4 : 2)
+void paged_attn_decode_kernel(
     uint16_t* __restrict__ out,          // [B, Hq, D] (used when nparts==1)
     float* __restrict__ tmp_out,         // [B, Hq, maxP, D]
     float* __restrict__ tmp_ml,          // [B, Hq, maxP, 2]
@@ -85,7 +105,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
     const uint16_t* __restrict__ v_cache,
     const int* __restrict__ block_tables,// [B, max_blocks]
     const int* __restrict__ seq_lens,    // [B]
-    float scale, int Hkv, int block_size, int max_blocks,
+    float scale, int Hkv, int bs_log2, int max_blocks,
     int partition_size, int max_parts, int window) {
   using CE = CacheElem<KV8>;
   using elem_t = typename CE::elem;
@@ -120,11 +140,50 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
   __shared__ float q_lds[G][DHEAD];
   __shared__ float s_lds[G][CHUNK];
   __shared__ float head_m[MAX_G], head_l[MAX_G], head_corr[MAX_G];
+  // Physical block ids of the chunk in flight, of the next one (its K
+  // rows are prefetched during this one) and of the one after (staged
+  // during this one): no K or V address waits on a block-table load.
+  // Entry i of a chunk's buffer is the block of token (first >> bs_log2)
+  // + i. Three buffers and not two, because a buffer is read from the K
+  // prefetch at the end of the previous chunk's phase A until the end
+  // of its own phase C, and with two the refill would need a barrier of
+  // its own; with three, the barriers that close each phase publish it.
+  __shared__ int blk_ids[3][IDS_MAX];
 
-  for (int idx = threadIdx.x; idx < G * DHEAD; idx += NTHREADS) {
-    const int g = idx / DHEAD, d = idx % DHEAD;
-    q_lds[g][d] =
-        bf16_to_f32(q[((int64_t)seq * Hq + hkv * G + g) * DHEAD + d]) * scale;
+  const int* btable = block_tables + (int64_t)seq * max_blocks;
+  const int bs_mask = (1 << bs_log2) - 1;
+  // The table entry thread t stages for the chunk at cbase. Every thread
+  // loads (no branch around the load, so the waits behind it stay
+  // counted); the index is clamped to the chunk's last block and only
+  // threads below IDS_MAX write theirs to LDS.
+  auto load_id = [&](int cbase) {
+    const int last = (min(cbase + CHUNK, p_end) - 1) >> bs_log2;
+    return btable[min((cbase >> bs_log2) + (int)threadIdx.x, last)];
+  };
+  // a partition of one chunk stages that chunk twice
+  const int id0 = load_id(p_start);
+  const int id1 = load_id(min(p_start + CHUNK, p_end - 1));
+
+  // q: the group's G rows are contiguous, one vector load per thread
+  {
+    constexpr int QV = G * DHEAD >= NTHREADS ? G * DHEAD / NTHREADS : 1;
+    typedef __attribute__((ext_vector_type(QV))) uint16_t qvec_t;
+    const int idx = threadIdx.x * QV;
+    if (idx < G * DHEAD) {
+      const uint16_t* qp = q + ((int64_t)seq * Hq + hkv * G) * DHEAD + idx;
+      float* dst = &q_lds[0][0] + idx;
+      if constexpr (QV == 1) {
+        dst[0] = bf16_to_f32(qp[0]) * scale;
+      } else {
+        const qvec_t raw = *reinterpret_cast<const qvec_t*>(qp);
+#pragma unroll
+        for (int i = 0; i < QV; ++i) dst[i] = bf16_to_f32(raw[i]) * scale;
+      }
+    }
+  }
+  if (threadIdx.x < IDS_MAX) {
+    blk_ids[0][threadIdx.x] = id0;
+    blk_ids[1][threadIdx.x] = id1;
   }
   if (threadIdx.x < MAX_G) {
     head_m[threadIdx.x] = -INFINITY;
@@ -139,16 +198,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
   constexpr int C_PAR = NTHREADS / NGRP;     // token parities (8 / 16)
   const int d8 = (threadIdx.x % NGRP) * 8;   // my dims [d8, d8+8)
   const int cpar = threadIdx.x / NGRP;
+  // Lets the compiler drop the one-row tail loop from the full chunks
+  // (npass is then a constant). Only where the registers need it: the
+  // bf16 G = 8 kernels spill without it (VPS = 8, D = 128: 18 VGPRs),
+  // while the smaller groups schedule worse with it (<128, 4, false, 4>
+  // goes from 168 to 182 VGPRs, one wave per SIMD less).
+  if constexpr (G == 8 && !KV8) __builtin_assume(cpar < C_PAR);
   float acc[G][8];
 #pragma unroll
   for (int g = 0; g < G; ++g)
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[g][i] = 0.f;
 
-  const int* btable = block_tables + (int64_t)seq * max_blocks;
   const int nwaves = NTHREADS / WAVE;
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
+
+  // Element offset of token tok's row for this kv head; tok lies in the
+  // chunk at cbase, whose block ids are in blk_ids[buf].
+  auto row_off = [&](int buf, int cbase, int tok) {
+    const int64_t blk =
+        blk_ids[buf][(tok >> bs_log2) - (cbase >> bs_log2)];
+    return (((blk * Hkv + hkv) << bs_log2) + (tok & bs_mask)) * DHEAD;
+  };
 
   // Raw K row for the chunk about to be scored, loaded one full chunk
   // ahead: the 16B loads stay live across phases B+C of the previous
@@ -156,23 +228,32 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
   // sinks the loads into the consume loop and ~2 are in flight per wave
   // (ISA audit, profiles/r02_decode_kpre.md).
   kvec_t kpre[DHEAD / KVEC];
-  auto issue_kpre = [&](int cbase) {
+  auto issue_kpre = [&](int buf, int cbase) {
     const int tok = min(cbase + (int)threadIdx.x, p_end - 1);
-    const int64_t roff =
-        (((int64_t)btable[tok / block_size] * Hkv + hkv) *
-             (int64_t)block_size + tok % block_size) * DHEAD;
-    const elem_t* krow = (const elem_t*)k_cache + roff;
+    const elem_t* krow = (const elem_t*)k_cache + row_off(buf, cbase, tok);
 #pragma unroll
     for (int j = 0; j < DHEAD / KVEC; ++j)
       kpre[j] = *reinterpret_cast<const kvec_t*>(krow + j * KVEC);
   };
-  issue_kpre(p_start);
+  issue_kpre(0, p_start);
 
-  for (int base = p_start; base < p_end; base += CHUNK) {
-    const int chunk_n = min(CHUNK, p_end - base);
+  // blk_ids buffer of this chunk, of the next and of the one after
+  int cur = 0, nxt = 1, aft = 2;
+
+  // One chunk. It is compiled twice, for the chunks that have a
+  // successor and for the partition's last chunk: with the K prefetch
+  // under a run-time condition the compiler cannot count the loads that
+  // are younger than a V batch and waits for all of them (vmcnt(0)),
+  // which drains the prefetch at the first V use. A chunk with a
+  // successor is also a full one, so its trip counts are constants.
+  auto do_chunk = [&](auto has_next, const int base) {
+    constexpr bool HAS_NEXT = decltype(has_next)::value;
+    const int chunk_n = HAS_NEXT ? CHUNK : p_end - base;
+    const int npass = (chunk_n - cpar + C_PAR - 1) / C_PAR;  // my V rows
+    auto vrow_off = [&](int tok) { return row_off(cur, base, tok) + d8; };
 
     // --- Phase A: scores -------------------------------------------------
-    if ((int)threadIdx.x < chunk_n) {
+    if (HAS_NEXT || (int)threadIdx.x < chunk_n) {
       float s[G];
 #pragma unroll
       for (int g = 0; g < G; ++g) s[g] = 0.f;
@@ -191,9 +272,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
 #pragma unroll
       for (int g = 0; g < G; ++g) s_lds[g][threadIdx.x] = s[g];
     }
-    // scores consumed: issue the NEXT chunk's K rows now so they fly
-    // during softmax + V accumulation
-    if (base + CHUNK < p_end) issue_kpre(base + CHUNK);
+    // Scores consumed. Issue the table loads for the chunk after the
+    // next first (they return first and go to LDS in phase C), then the
+    // NEXT chunk's K rows, which fly during softmax + V accumulation.
+    const bool stage_ids = HAS_NEXT && base + 2 * CHUNK < p_end;
+    int id_aft = 0;
+    if constexpr (HAS_NEXT)
+      id_aft = load_id(min(base + 2 * CHUNK, p_end - 1));
+    if constexpr (HAS_NEXT) issue_kpre(nxt, base + CHUNK);
     __syncthreads();
 
     // --- Phase B: online softmax per head --------------------------------
@@ -229,12 +315,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
       for (int g = 0; g < G; ++g)
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[g][i] *= head_corr[g];
-      const int npass = (chunk_n - cpar + C_PAR - 1) / C_PAR;  // my tokens
-      auto vrow_off = [&](int tok) {
-        const int64_t blk = btable[tok / block_size];
-        return (((blk * Hkv + hkv) * (int64_t)block_size +
-                 tok % block_size)) * DHEAD + d8;
-      };
+      // read next at the end of the next chunk's phase A: the barrier
+      // that closes this phase publishes it
+      if (stage_ids && threadIdx.x < IDS_MAX)
+        blk_ids[aft][threadIdx.x] = id_aft;
       auto load_v = [&](int64_t off, float v[8]) {
         const vvec_t raw =
             *reinterpret_cast<const vvec_t*>((const elem_t*)v_cache + off);
@@ -301,7 +385,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void paged_attn_decode_kernel(
       }
     }
     __syncthreads();
-  }
+    const int t = cur;
+    cur = nxt;
+    nxt = aft;
+    aft = t;
+  };
+  int base = p_start;
+  for (; base + CHUNK < p_end; base += CHUNK)
+    do_chunk(std::true_type{}, base);
+  do_chunk(std::false_type{}, base);
 
   // Combine the C_PAR token parities via LDS, then write out.
   __shared__ float comb[G * DHEAD];
@@ -391,14 +483,14 @@ template <int DHEAD, int G>
 void launch_decode(uint16_t* out, float* tmp_out, float* tmp_ml,
                    const uint16_t* q, const uint16_t* kc, const uint16_t* vc,
                    const int* bt, const int* lens, float scale, int B,
-                   int Hkv, int block_size, int max_blocks, int eff_part,
+                   int Hkv, int bs_log2, int max_blocks, int eff_part,
                    int nparts, int max_parts, int window, bool kv8,
                    hipStream_t stream) {
 #define LAUNCH_PD(K8, VPS)                                                   \
   hipLaunchKernelGGL((paged_attn_decode_kernel<DHEAD, G, K8, VPS>),          \
                      dim3(B, Hkv, nparts), dim3(NTHREADS), 0, stream, out,   \
                      tmp_out, tmp_ml, q, kc, vc, bt, lens, scale, Hkv,       \
-                     block_size, max_blocks, eff_part, max_parts, window)
+                     bs_log2, max_blocks, eff_part, max_parts, window)
   // Measured in profiles/r02_decode_kpre.md. A grid under 2048
   // workgroups underfills the chip (256 CUs x 4 SIMDs), so
   // per-wave depth has to replace occupancy-based latency hiding: the
@@ -433,6 +525,13 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
   const int G = Hq / Hkv;
   TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "G must be 1/2/4/8");
   TORCH_CHECK(max_len >= 1, "max_len must be >= 1, got ", max_len);
+  // the kernel addresses a token with shift and mask, and a chunk's
+  // block ids have IDS_MAX slots in LDS
+  TORCH_CHECK(block_size >= MIN_BS && (block_size & (block_size - 1)) == 0,
+              "KV cache block_size must be a power of two and at least ",
+              MIN_BS, ", got ", block_size);
+  int bs_log2 = 0;
+  while ((1 << bs_log2) < block_size) ++bs_log2;
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
                   out.scalar_type() == torch::kBFloat16,
               "q and out must be bf16");
@@ -449,6 +548,8 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
                   block_tables.is_contiguous() && seq_lens.is_contiguous() &&
                   tmp_out.is_contiguous() && tmp_ml.is_contiguous(),
               "paged_attn_decode takes contiguous tensors");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q must be 16-byte aligned (it is read with vector loads)");
   TORCH_CHECK(tmp_out.scalar_type() == torch::kFloat32 && max_parts >= 1 &&
                   tmp_out.sizes() == at::IntArrayRef({B, Hq, max_parts, D}),
               "tmp_out must be fp32 [B, Hq, max_parts, D] with B = ", B,
@@ -480,7 +581,7 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
   const bool kv8 = k_cache.scalar_type() == torch::kUInt8;
 #define DISPATCH(DH, GG)                                                     \
   launch_decode<DH, GG>(o, to, tm, qp, kp, vp, bp, lp, (float)scale, B,     \
-                        Hkv, block_size, max_blocks, eff_part, nparts,      \
+                        Hkv, bs_log2, max_blocks, eff_part, nparts,         \
                         max_parts, (int)window, kv8, stream)
   if (D == 128) {
     if (G == 1) DISPATCH(128, 1);

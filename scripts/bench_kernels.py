@@ -33,7 +33,9 @@ def bench_decode():
     print("== paged_attn_decode ==")
     for (B, hq, hkv, d, L) in [(64, 32, 8, 128, 560), (64, 32, 8, 128, 2048),
                                (1, 32, 8, 128, 2048), (8, 32, 8, 128, 8192),
-                               (256, 32, 8, 128, 560)]:
+                               (256, 32, 8, 128, 560),
+                               # what bench.py runs: B=512, prompt 512
+                               (512, 32, 8, 128, 620)]:
         bs = 16
         nb = (L + bs - 1) // bs
         total_blocks = B * nb + 1
