@@ -94,6 +94,20 @@ class LLMEngine:
         self.tp_size = tp_size
         self.tp_rank = tp_rank
         self.tp_group = tp_group
+        if self.model_cfg.num_experts > 0:
+            # MoE experts are served in bf16 on one GPU only (docs/KERNELS.md
+            # "moe.hip": out of scope); refuse before allocating anything
+            bad = [what for what, on in (
+                (f"quantization={cfg.quantization!r}",
+                 cfg.quantization is not None),
+                (f"max_loras={cfg.max_loras}", cfg.max_loras > 0),
+                (f"tp_size={tp_size}", tp_size > 1)) if on]
+            if bad:
+                raise ValueError(
+                    f"model {cfg.model!r} is a mixture of experts: "
+                    f"{', '.join(bad)} is not supported (quantised experts, "
+                    "LoRA on experts and tensor-parallel experts are not "
+                    "implemented)")
         if model is None:
             dtype = torch.bfloat16
             model = LlamaForCausalLM(self.model_cfg, tp_size, tp_rank)

@@ -99,6 +99,19 @@ def _map_hf_name(name: str):
         }
         if rest in m:
             return m[rest]
+        # HF Mixtral: block_sparse_moe.gate + experts.{e}.w1 (gate) / w3
+        # (up) / w2 (down), packed into the stacked expert parameters; the
+        # role carries the expert index
+        if rest == "block_sparse_moe.gate.weight":
+            return f"layers.{i}.mlp.router_w", None
+        if len(parts) == 7 and parts[2:4] == ["block_sparse_moe", "experts"] \
+                and parts[4].isdigit() and parts[6] == "weight" \
+                and parts[5] in ("w1", "w2", "w3"):
+            e = int(parts[4])
+            if parts[5] == "w2":
+                return f"layers.{i}.mlp.w2", ("expert_down", e)
+            return (f"layers.{i}.mlp.w13",
+                    ("expert_gate" if parts[5] == "w1" else "expert_up", e))
     return name, None  # our native names pass through
 
 
@@ -179,6 +192,17 @@ def load_llama_weights(model, ckpt_dir: str, use_async: bool = True,
             stage_copy(p.data[:inter], tensor)
         elif role == "up":
             stage_copy(p.data[inter:], tensor)
+        elif isinstance(role, tuple):
+            kind, e = role
+            if not 0 <= e < p.shape[0]:
+                raise ValueError(f"{name}: expert {e} but the model has "
+                                 f"{p.shape[0]} experts")
+            if kind == "expert_gate":
+                stage_copy(p.data[e, :inter], tensor)
+            elif kind == "expert_up":
+                stage_copy(p.data[e, inter:], tensor)
+            else:
+                stage_copy(p.data[e], tensor)
         else:
             stage_copy(p.data, tensor)
         loaded += 1

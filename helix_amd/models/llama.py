@@ -39,6 +39,8 @@ class LlamaConfig:
     sliding_window: int = 0        # 0 = full attention (Mistral v0.1: 4096)
     attention_bias: bool = False   # Qwen2-style QKV bias
     rope_scaling: dict = field(default_factory=dict)  # llama3.1 scheme
+    num_experts: int = 0           # 0 = dense MLP; > 0 = Mixtral-style MoE
+    experts_per_token: int = 2
 
     @property
     def q_size(self) -> int:
@@ -88,6 +90,18 @@ PRESETS = {
         intermediate_size=512, num_layers=2, num_heads=4, num_kv_heads=2,
         head_dim=64, max_position=512, rope_base=10000.0,
         sliding_window=24),
+    # Mixtral-8x7B (v0.1): 8 SwiGLU experts per layer, top-2 routing, no
+    # sliding window
+    "mixtral-8x7b": LlamaConfig(
+        name="mixtral-8x7b", vocab_size=32000, hidden_size=4096,
+        intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8,
+        head_dim=128, rope_base=1000000.0, max_position=32768,
+        num_experts=8, experts_per_token=2),
+    "tiny-moe": LlamaConfig(
+        name="tiny-moe", vocab_size=512, hidden_size=256,
+        intermediate_size=256, num_layers=2, num_heads=4, num_kv_heads=2,
+        head_dim=64, max_position=512, rope_base=10000.0,
+        num_experts=8, experts_per_token=2),
 }
 
 
@@ -230,13 +244,40 @@ class MLP(nn.Module):
         return out
 
 
+class MoEMLP(nn.Module):
+    """Mixtral-style sparse MLP: a router over E SwiGLU experts, the top
+    `experts_per_token` of them per token (ops.moe_forward). The weights are
+    plain Parameters, not nn.Linear, so the quantisers' and the LoRA
+    manager's nn.Linear walks never see them; expert weights are neither
+    quantised, adapted nor sharded."""
+
+    def __init__(self, cfg: LlamaConfig):
+        super().__init__()
+        e, h, i = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
+        self.k = cfg.experts_per_token
+        # created in bf16, the one dtype the kernels serve: mixtral-8x7b's
+        # 45 G expert weights never exist in fp32, on the host or the GPU
+        bf16 = torch.bfloat16
+        self.router_w = nn.Parameter(torch.empty(e, h, dtype=bf16))
+        # gate rows [:I], up rows [I:]
+        self.w13 = nn.Parameter(torch.empty(e, 2 * i, h, dtype=bf16))
+        self.w2 = nn.Parameter(torch.empty(e, h, i, dtype=bf16))
+
+    def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
+        router_logits = F.linear(x, self.router_w)
+        # decode runs under hipGraph capture: always the fused kernels there
+        fused = True if not getattr(meta, "is_prefill", True) else None
+        return ops.moe_forward(x, router_logits, self.w13, self.w2, self.k,
+                               fused=fused)
+
+
 class DecoderLayer(nn.Module):
     def __init__(self, cfg: LlamaConfig, tp_size: int = 1, tp_rank: int = 0):
         super().__init__()
         self.input_norm_w = nn.Parameter(torch.ones(cfg.hidden_size))
         self.post_norm_w = nn.Parameter(torch.ones(cfg.hidden_size))
         self.attn = Attention(cfg, tp_size, tp_rank)
-        self.mlp = MLP(cfg, tp_size)
+        self.mlp = MoEMLP(cfg) if cfg.num_experts > 0 else MLP(cfg, tp_size)
         self.eps = cfg.rms_norm_eps
 
     def forward(self, x, residual, cos_sin, kv_cache, meta):

@@ -487,6 +487,141 @@ def gemm_kq(x: torch.Tensor, planes, fmt: str,
     return out
 
 
+# -- mixture-of-experts routed expert GEMMs (ops/hip/moe.hip) -----------
+# Largest T at which moe_experts(fused=None) takes the fused kernels; above
+# it the eager library path runs (one host sync, so never under capture;
+# decode passes fused=True). The rule: the largest benchmarked T at which
+# the fused path is not slower than the library path on uniform routing, in
+# two runs of scripts/bench_moe.py (T = 1, 8, 16, 64, 128, 512).
+# MEASURED, not the placeholder of 64 (profiles/r08_moe.md): fused over
+# library on uniform routing 2.2x at T = 1, 1.4x at 64, 1.1x at 128 and
+# 0.47x at 512 in both runs.
+MOE_FUSED_MAX_T = 128
+
+
+def moe_waves(N: int, K: int, gated: bool) -> int:
+    """K-split factor (waves per workgroup) the routed GEMM uses for one
+    expert's [N, K] weight (N = I, K = H for the gated GEMM; N = H, K = I
+    for the down GEMM): the host's own function, a property of the shape."""
+    return int(_native().moe_waves(N, K, gated))
+
+
+def moe_route(logits: torch.Tensor, k: int):
+    """(topk_ids [T, k] int32, topk_w [T, k] fp32): fp32 softmax over the
+    experts, the k largest renormalised to sum 1, ties to the lower expert
+    index, slot j = the j-th largest."""
+    if not logits.is_cuda:
+        return ref.moe_route(logits, k)
+    T = logits.shape[0]
+    ids = torch.empty(T, k, dtype=torch.int32, device=logits.device)
+    w = torch.empty(T, k, dtype=torch.float32, device=logits.device)
+    _native().moe_route(ids, w, logits)
+    return ids, w
+
+
+def moe_align(topk_ids: torch.Tensor, E: int):
+    """(expert_off [E+1] int32, sorted_pairs [P] int32): per expert, its
+    pair indices p = t*k + j in ascending order. Ids outside [0, E) belong
+    to no list (sorted_pairs past expert_off[E] is then unspecified on GPU)."""
+    if not topk_ids.is_cuda:
+        return ref.moe_align(topk_ids, E)
+    off = torch.empty(E + 1, dtype=torch.int32, device=topk_ids.device)
+    pairs = torch.empty(topk_ids.numel(), dtype=torch.int32,
+                        device=topk_ids.device)
+    _native().moe_align(off, pairs, topk_ids, E)
+    return off, pairs
+
+
+def moe_combine(ypair: torch.Tensor, k: int,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[t] = bf16(sum_j ypair[t*k + j]), ascending j, in fp32."""
+    if not ypair.is_cuda:
+        return ref.moe_combine(ypair, k)
+    if out is None:
+        out = torch.empty(ypair.shape[0] // k, ypair.shape[1],
+                          dtype=torch.bfloat16, device=ypair.device)
+    _native().moe_combine(out, ypair, k)
+    return out
+
+
+def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+                topk_ids: torch.Tensor, topk_w: torch.Tensor,
+                fused: bool | None = None, out: torch.Tensor | None = None,
+                act: torch.Tensor | None = None,
+                ypair: torch.Tensor | None = None) -> torch.Tensor:
+    """Routed SwiGLU experts: out[t] = sum_j topk_w[t, j] *
+    w2[e] @ (silu(w13[e, :I] @ x[t]) * (w13[e, I:] @ x[t])), e = topk_ids[t, j].
+    x [T, H] bf16, w13 [E, 2I, H], w2 [E, H, I], topk_ids int32 in [0, E)
+    (a pair with any other id is computed by no expert and its share of the
+    sum is unspecified).
+    GPU, fused=True: moe_align + the two routed GEMM kernels + moe_combine;
+    no host sync, no host-sized shape, no memset, so always capture-safe,
+    and correct for any T. GPU, fused=False: the eager library path (one
+    host sync): x gathered by list, per-expert F.linear / silu_and_mul /
+    F.linear, scaled into the same fp32 ypair, the same moe_combine.
+    fused=None: fused up to MOE_FUSED_MAX_T tokens. `out` [T, H] bf16, `act`
+    [T*k, I] bf16 and `ypair` [T*k, H] fp32 are allocated when None.
+    CPU: the torch reference."""
+    if not x.is_cuda:
+        return ref.moe_experts(x, w13, w2, topk_ids, topk_w)
+    if x.dim() != 2 or topk_ids.dim() != 2:
+        raise ValueError("moe_experts: x must be [T, H] and topk_ids [T, k]")
+    T, k = topk_ids.shape
+    E, I, H = w13.shape[0], w13.shape[1] // 2, w13.shape[2]
+    P = T * k
+    if x.shape[0] != T or tuple(topk_w.shape) != (T, k):
+        raise ValueError(
+            f"moe_experts: x {tuple(x.shape)}, topk_ids {tuple(topk_ids.shape)}"
+            f" and topk_w {tuple(topk_w.shape)} disagree on [T, k]")
+    if fused is None:
+        fused = T <= MOE_FUSED_MAX_T
+    if act is None:
+        act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
+    if ypair is None:
+        ypair = torch.empty(P, H, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(T, H, dtype=torch.bfloat16, device=x.device)
+    C = _native()
+    off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
+    pairs = torch.empty(P, dtype=torch.int32, device=x.device)
+    C.moe_align(off, pairs, topk_ids, E)
+    if fused:
+        C.moe_gemm_gated(act, x, w13, off, pairs, k)
+        C.moe_gemm_down(ypair, act, w2, topk_w, off, pairs)
+    else:
+        if x.dtype != torch.bfloat16 or w13.dtype != torch.bfloat16 \
+                or w2.dtype != torch.bfloat16:
+            raise ValueError("moe_experts: x, w13 and w2 must be bf16 on GPU")
+        if tuple(w2.shape) != (E, H, I) or x.shape[1] != H \
+                or tuple(act.shape) != (P, I) or tuple(ypair.shape) != (P, H) \
+                or ypair.dtype != torch.float32:
+            raise ValueError("moe_experts: shape mismatch between x, w13, w2,"
+                             " act and ypair")
+        offs = off.tolist()                       # the one host sync
+        rows = pairs[:offs[E]].long()
+        xg = x[rows // k]
+        tw = topk_w.reshape(-1)[rows]
+        for e in range(E):
+            lo, hi = offs[e], offs[e + 1]
+            if hi == lo:
+                continue
+            a = silu_and_mul(torch.nn.functional.linear(xg[lo:hi], w13[e]))
+            act[rows[lo:hi]] = a
+            y = torch.nn.functional.linear(a, w2[e])
+            ypair[rows[lo:hi]] = y.float() * tw[lo:hi, None]
+    C.moe_combine(out, ypair, k)
+    return out
+
+
+def moe_forward(x: torch.Tensor, router_logits: torch.Tensor,
+                w13: torch.Tensor, w2: torch.Tensor, k: int,
+                fused: bool | None = None) -> torch.Tensor:
+    """One MoE MLP: route (moe_route) and run the routed experts
+    (moe_experts)."""
+    ids, w = moe_route(router_logits, k)
+    return moe_experts(x, w13, w2, ids, w, fused=fused)
+
+
 def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)

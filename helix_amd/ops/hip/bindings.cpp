@@ -71,6 +71,21 @@ void dequant_kq(torch::Tensor out, std::vector<torch::Tensor> planes,
                 std::string fmt);
 int64_t kq_kernel_max_m();
 int64_t kq_waves(int64_t N, int64_t K);
+void moe_route(torch::Tensor topk_ids, torch::Tensor topk_w,
+               torch::Tensor logits);
+void moe_align(torch::Tensor expert_off, torch::Tensor sorted_pairs,
+               torch::Tensor topk_ids, int64_t E);
+void moe_gemm_gated(torch::Tensor act, torch::Tensor x, torch::Tensor w13,
+                    torch::Tensor expert_off, torch::Tensor sorted_pairs,
+                    int64_t k);
+void moe_gemm_down(torch::Tensor ypair, torch::Tensor act, torch::Tensor w2,
+                   torch::Tensor topk_w, torch::Tensor expert_off,
+                   torch::Tensor sorted_pairs);
+void moe_combine(torch::Tensor out, torch::Tensor ypair, int64_t k);
+int64_t moe_waves(int64_t N, int64_t K, bool gated);
+int64_t moe_max_experts();
+int64_t moe_max_topk();
+int64_t moe_chunk_pairs();
 void mfma_probe(torch::Tensor d, torch::Tensor a, torch::Tensor b);
 torch::Tensor ar_create(int64_t world, int64_t rank, int64_t capacity);
 void ar_open(std::vector<torch::Tensor> handles);
@@ -123,6 +138,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kq_waves", &kq_waves,
         "K-split factor (waves per workgroup) gemm_kq uses for a [N,K] weight");
   m.attr("KQ_KERNEL_MAX_M") = kq_kernel_max_m();
+  m.def("moe_route", &moe_route,
+        "MoE routing: fp32 softmax, top-k (ties to the lower expert), "
+        "renormalised weights");
+  m.def("moe_align", &moe_align,
+        "MoE pair lists: expert_off[E+1] and per-expert ascending pair ids");
+  m.def("moe_gemm_gated", &moe_gemm_gated,
+        "Routed expert GEMM 1: act[p] = silu(x[p/k] @ gate_e^T) * (x[p/k] @ "
+        "up_e^T)");
+  m.def("moe_gemm_down", &moe_gemm_down,
+        "Routed expert GEMM 2: ypair[p] = topk_w[p] * (act[p] @ w2_e^T), fp32");
+  m.def("moe_combine", &moe_combine,
+        "out[t] = bf16(sum over slots of ypair[t*k + j]), fixed order");
+  m.def("moe_waves", &moe_waves,
+        "K-split factor (waves per workgroup) moe_gemm uses for one expert's "
+        "[N, K] weight");
+  m.attr("MOE_MAX_EXPERTS") = moe_max_experts();
+  m.attr("MOE_MAX_TOPK") = moe_max_topk();
+  m.attr("MOE_CHUNK_PAIRS") = moe_chunk_pairs();
   m.def("mfma_probe", &mfma_probe, "16x16x32 MFMA layout probe");
   m.def("ar_create", &ar_create,
         "Allocate one-shot allreduce mailbox; returns IPC handle bytes");

@@ -505,3 +505,69 @@ def unpack_ggml_kq(raw, shape, fmt: str):
             b[..., 128:192].contiguous().reshape(N, K // 4),
             b[..., 192:208].contiguous().view(torch.int8).reshape(N, K // 16),
             b[..., 208:210].contiguous().view(torch.float16).reshape(N, nb))
+
+
+# -- mixture of experts (ops/hip/moe.hip) --------------------------------
+
+def moe_route(logits: torch.Tensor, k: int):
+    """Mixtral routing: fp32 softmax over the E experts, the k largest kept
+    and renormalised to sum 1. Slot j holds the j-th largest expert; equal
+    logits go to the lower expert index (a stable descending sort).
+    Returns (topk_ids [T, k] int32, topk_w [T, k] fp32)."""
+    lf = logits.float()
+    order = torch.sort(lf, dim=-1, descending=True, stable=True).indices
+    ids = order[:, :k]
+    p = torch.softmax(lf, dim=-1).gather(-1, ids)
+    return ids.to(torch.int32), p / p.sum(-1, keepdim=True)
+
+
+def moe_align(topk_ids: torch.Tensor, E: int):
+    """(expert_off [E+1] int32, sorted_pairs [P] int32): for each expert its
+    pair indices (p = t*k + j) in ascending order. Ids outside [0, E)
+    belong to no list; the tail of sorted_pairs past expert_off[E] is 0."""
+    flat = topk_ids.reshape(-1).long()
+    P = flat.numel()
+    valid = (flat >= 0) & (flat < E)
+    key = torch.where(valid, flat, torch.full_like(flat, E))
+    order = torch.sort(key, stable=True).indices
+    counts = torch.bincount(key, minlength=E + 1)[:E]
+    off = torch.zeros(E + 1, dtype=torch.int64, device=flat.device)
+    off[1:] = counts.cumsum(0)
+    pairs = order.clone()
+    pairs[int(off[E]):] = 0
+    assert pairs.numel() == P
+    return off.to(torch.int32), pairs.to(torch.int32)
+
+
+def moe_combine(ypair: torch.Tensor, k: int) -> torch.Tensor:
+    """out[t] = bf16(sum_j ypair[t*k + j]) in ascending j, fp32."""
+    P, H = ypair.shape
+    y = ypair.float().view(P // k, k, H)
+    out = y[:, 0].clone()
+    for j in range(1, k):
+        out += y[:, j]
+    return out.to(torch.bfloat16)
+
+
+def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+                topk_ids: torch.Tensor, topk_w: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum_j topk_w[t, j] * down_e(silu(gate_e(x[t])) * up_e(x[t])),
+    e = topk_ids[t, j]. Rounds where the kernels round: fp32 accumulation,
+    the activation to bf16, fp32 per-pair results, one rounding of the sum."""
+    T, k = topk_ids.shape
+    E, I2, H = w13.shape
+    I = I2 // 2
+    off, pairs = moe_align(topk_ids, E)
+    off = off.tolist()
+    ypair = torch.zeros(T * k, H, dtype=torch.float32, device=x.device)
+    xf = x.float()
+    twf = topk_w.reshape(-1).float()
+    for e in range(E):
+        p = pairs[off[e]:off[e + 1]].long()
+        if p.numel() == 0:
+            continue
+        gu = xf[p // k] @ w13[e].float().t()
+        act = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]) \
+            .to(torch.bfloat16)
+        ypair[p] = (act.float() @ w2[e].float().t()) * twf[p, None]
+    return moe_combine(ypair, k).to(x.dtype)

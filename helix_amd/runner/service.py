@@ -55,6 +55,9 @@ DEFAULT_SPECS = {
     "mistral-7b": ModelSpec("mistral-7b", "llm", "mistral-7b"),
     "qwen2-7b": ModelSpec("qwen2-7b", "llm", "qwen2-7b",
                           max_model_len=32768),
+    # ~93 GB of bf16 weights on one MI355X; KV from what is left
+    "mixtral-8x7b": ModelSpec("mixtral-8x7b", "llm", "mixtral-8x7b",
+                              max_model_len=32768, kv_cache_blocks=16384),
     "bge-base": ModelSpec("bge-base", "embedding", "bge-base"),
     "siglip-base": ModelSpec("siglip-base", "vision", "siglip-base"),
     "tiny-vit": ModelSpec("tiny-vit", "vision", "tiny-vit"),
@@ -65,6 +68,8 @@ DEFAULT_SPECS = {
     "tiny": ModelSpec("tiny", "llm", "tiny", max_model_len=256,
                       kv_cache_blocks=256),
     "tiny-gqa": ModelSpec("tiny-gqa", "llm", "tiny-gqa", max_model_len=512,
+                          kv_cache_blocks=256),
+    "tiny-moe": ModelSpec("tiny-moe", "llm", "tiny-moe", max_model_len=256,
                           kv_cache_blocks=256),
     "tiny-bert": ModelSpec("tiny-bert", "embedding", "tiny-bert"),
 }
@@ -98,9 +103,12 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
         return 2 * (n + cfg.num_layers * per_layer) + (64 << 20)
     cfg = LLAMA_PRESETS[spec.preset]
     emb = cfg.vocab_size * cfg.hidden_size * (1 if cfg.tie_embeddings else 2)
+    mlp = 3 * cfg.hidden_size * cfg.intermediate_size
+    if cfg.num_experts > 0:         # E experts + the [E, H] router
+        mlp = cfg.num_experts * (mlp + cfg.hidden_size)
     per_layer = (cfg.hidden_size * (cfg.q_size + 2 * cfg.kv_size)  # qkv
                  + cfg.q_size * cfg.hidden_size                     # o
-                 + 3 * cfg.hidden_size * cfg.intermediate_size)     # mlp
+                 + mlp)
     # projection bytes per 256 weights: bf16 512, fp8 256, ggml blocks
     # 8 x 34 / 8 x 18, K-quant super-blocks 144 / 210 (embeddings/lm_head
     # stay bf16)
@@ -468,7 +476,10 @@ class RunnerService:
         """Admission control: load `model`, LRU-evicting idle models if the
         estimate does not fit in free HBM. Raises NoCapacityError if it
         cannot fit even after eviction (control plane surfaces 503,
-        matching the reference's NoRunnerError behavior, router.go:62)."""
+        matching the reference's NoRunnerError behavior, router.go:62).
+        A catalog alias (helix-mixtral, ...) loads the model it names."""
+        from helix_amd.server.models_catalog import resolve_model_name
+        model = resolve_model_name(model)
         with self._lock:
             if model in self.instances:
                 return self.instances[model]

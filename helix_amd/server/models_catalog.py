@@ -24,6 +24,9 @@ STATIC_MODEL_INFO: Dict[str, dict] = {
     "qwen2-7b": {"context_length": 32768, "prompt_price_per_m": 0.05,
                  "completion_price_per_m": 0.10, "family": "qwen",
                  "runtime": "helix_amd", "kind": "chat"},
+    "mixtral-8x7b": {"context_length": 32768, "prompt_price_per_m": 0.3,
+                     "completion_price_per_m": 0.5, "family": "mixtral",
+                     "runtime": "helix_amd", "kind": "chat"},
     "bge-base": {"context_length": 512, "prompt_price_per_m": 0.005,
                  "completion_price_per_m": 0.0, "family": "bge",
                  "runtime": "helix_amd", "kind": "embedding"},
@@ -48,12 +51,28 @@ STATIC_MODEL_INFO: Dict[str, dict] = {
 }
 
 
+# Names a reference deployment asks for -> the catalog id that serves them
+# (api/pkg/model/models.go: helix-mixtral -> mixtral:instruct; config.go
+# defaults APPS_MODEL and FINETUNING_QA_PAIR_GEN_MODEL to the HF name).
+MODEL_ALIASES: Dict[str, str] = {
+    "helix-mixtral": "mixtral-8x7b",
+    "mixtral:instruct": "mixtral-8x7b",
+    "mistralai/Mixtral-8x7B-Instruct-v0.1": "mixtral-8x7b",
+}
+
+
+def resolve_model_name(model: str) -> str:
+    """An alias -> its catalog id; any other name unchanged."""
+    return MODEL_ALIASES.get(model, model)
+
+
 class ModelCatalog:
     def __init__(self, store):
         self.store = store
 
     def get(self, model: str) -> Optional[dict]:
         """Dynamic DB override wins over the static catalog."""
+        model = resolve_model_name(model)
         dyn = self.store.get("models", model)
         if dyn:
             base = dict(STATIC_MODEL_INFO.get(model, {}))

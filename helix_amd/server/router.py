@@ -8,6 +8,7 @@ import threading
 import time
 from typing import Dict, List, Optional
 
+from helix_amd.server.models_catalog import resolve_model_name
 from helix_amd.server.types import RunnerHeartbeat, RunnerState
 
 
@@ -68,7 +69,9 @@ class InferenceRouter:
 
     def pick_runner(self, model: str) -> str:
         """Per-model round-robin over fresh runners serving it
-        (reference router.go:168-198). Returns the runner address."""
+        (reference router.go:168-198). Returns the runner address. A
+        catalog alias (helix-mixtral, ...) picks the runners of its model."""
+        model = resolve_model_name(model)
         with self._lock:
             cands = [r for r in self._fresh()
                      if any(m.model_id == model and m.state == "ready"

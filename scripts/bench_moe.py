@@ -1,0 +1,131 @@
+#!/usr/bin/env python
+"""Mixture-of-experts layer benchmark: the fused routed-GEMM kernels against
+the eager library path.
+
+Times ops.moe_forward (route + lists + experts + combine) with fused=True
+and fused=False on one Mixtral-shaped MoE layer (E 8, k 2, H 4096, I 14336
+unless given) at decode and prefill token counts, under two routings:
+  uniform  random router logits
+  skewed   every token's first choice is expert 0, the second one random
+and prints one JSON line per (T, routing, path): median and min
+microseconds per call, and for the fused path the bytes of the distinct
+activated experts' weights per second that time corresponds to.
+
+Method: device events around a window of `--iters` back-to-back calls,
+`--rounds` windows per path with the two paths interleaved inside one
+process, after a warm-up of every shape. Each call uses the next of several
+copies of the layer's weights (more than the 256 MiB last-level cache
+between two uses of a weight), as consecutive layers of a model would. The
+library path's host sync is inside its window: it is part of that path.
+
+A GPU is required; there is no CPU fallback. Run under a time limit, e.g.
+    timeout 600 python scripts/bench_moe.py --out moe.jsonl
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import helix_amd.ops as ops  # noqa: E402
+
+TS = [1, 8, 16, 64, 128, 512]
+ROUTINGS = ("uniform", "skewed")
+CACHE_BYTES = 768 << 20       # rotate over at least this many weight bytes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--experts", type=int, default=8)
+    ap.add_argument("--topk", type=int, default=2)
+    ap.add_argument("--hidden", type=int, default=4096)
+    ap.add_argument("--inter", type=int, default=14336)
+    ap.add_argument("--t", type=int, action="append")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_moe.py needs a GPU")
+    assert ops.have_native(), "native extension is not built"
+    dev = torch.device("cuda:0")
+    E, k, H, I = args.experts, args.topk, args.hidden, args.inter
+    expert_bytes = 3 * H * I * 2
+    # the least a call activates is k experts; keep two uses of a weight
+    # more than the last-level cache apart
+    copies = max(2, -(-CACHE_BYTES // (k * expert_bytes)))
+    g = torch.Generator(device=dev).manual_seed(E + H + I)
+    layers = []
+    for _ in range(copies):
+        w13 = torch.empty(E, 2 * I, H, dtype=torch.bfloat16, device=dev)
+        w2 = torch.empty(E, H, I, dtype=torch.bfloat16, device=dev)
+        w13.normal_(0.0, H ** -0.5, generator=g)
+        w2.normal_(0.0, I ** -0.5, generator=g)
+        layers.append((w13, w2))
+
+    def call(fused, x, logits, i):
+        w13, w2 = layers[i % copies]
+        return ops.moe_forward(x, logits, w13, w2, k, fused=fused)
+
+    lines = []
+    for T in args.t or TS:
+        for routing in ROUTINGS:
+            x = torch.randn(T, H, generator=g, device=dev).to(torch.bfloat16)
+            logits = torch.randn(T, E, generator=g, device=dev)
+            if routing == "skewed":
+                logits[:, 0] += 100.0
+            logits = logits.to(torch.bfloat16)
+            ids, _ = ops.moe_route(logits, k)
+            counts = torch.bincount(ids.reshape(-1).long(), minlength=E)
+            distinct = int((counts > 0).sum())
+            paths = {"fused": True, "library": False}
+            got = {}
+            for name, fused in paths.items():               # warm-up
+                for i in range(2 * copies + 3):
+                    got[name] = call(fused, x, logits, i)
+            torch.cuda.synchronize()
+            # the two paths agree on what they compute (same weights: both
+            # ended the warm-up on the same copy)
+            diff = (got["fused"].float() - got["library"].float()).abs().max()
+            scale = got["library"].float().abs().max()
+            times = {name: [] for name in paths}
+            for _ in range(args.rounds):
+                for name, fused in paths.items():
+                    t0 = torch.cuda.Event(enable_timing=True)
+                    t1 = torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    for i in range(args.iters):
+                        call(fused, x, logits, i)
+                    t1.record()
+                    t1.synchronize()
+                    times[name].append(
+                        t0.elapsed_time(t1) * 1e3 / args.iters)
+            lib_med = statistics.median(times["library"])
+            for name, ts in times.items():
+                med, mn = statistics.median(ts), min(ts)
+                rec = {"E": E, "k": k, "H": H, "I": I, "T": T,
+                       "routing": routing, "path": name,
+                       "us_median": round(med, 1), "us_min": round(mn, 1),
+                       "distinct_experts": distinct,
+                       "longest_list": int(counts.max()),
+                       "weight_bytes": distinct * expert_bytes,
+                       "weight_GBps": round(
+                           distinct * expert_bytes / med / 1e3, 1),
+                       "speedup_vs_library": round(lib_med / med, 3),
+                       "max_abs_diff_over_max": round(
+                           float(diff / scale), 5)}
+                line = json.dumps(rec)
+                print(line, flush=True)
+                lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
