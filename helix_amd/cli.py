@@ -488,14 +488,19 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
                     "", "--quant", help="q4_0 | q8_0 | q4_k | q6_k: quantize "
                     "the projection weights (norms/embeddings stay as they "
                     "are); q4_k_m: llama.cpp's Q4_K/Q6_K mix, output.weight "
-                    "Q6_K and token_embd Q4_K")):
+                    "Q6_K and token_embd Q4_K. On a mixture-of-experts "
+                    "preset q4_0 / q8_0 also quantize the merged expert "
+                    "tensors; the K-quant flags leave them bf16"),
+                experts_only: bool = typer.Option(
+                    False, "--experts-only", help="with --quant q4_0 | "
+                    "q8_0 on a mixture of experts: quantize the expert "
+                    "tensors alone")):
     """Export a model as a GGUF v3 checkpoint (llama.cpp tensor names,
     Q/K rows permuted for GGML rope — interops with the llama.cpp
     ecosystem; see engine/gguf.py)."""
     if quant not in ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m"):
         raise typer.BadParameter(
             "--quant must be q4_0, q8_0, q4_k, q6_k or q4_k_m")
-    import torch
     from helix_amd.engine import gguf as g
     from helix_amd.models.llama import LlamaForCausalLM, PRESETS
 
@@ -507,71 +512,10 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
     else:
         model.init_random(seed)
 
-    def permute(w, n_head):
-        o, i = w.shape
-        return (w.reshape(n_head, 2, o // n_head // 2, i)
-                .swapaxes(1, 2).reshape(o, i))
-
-    sd = dict(model.named_parameters())
-    q, kv, inter = cfg.q_size, cfg.kv_size, cfg.intermediate_size
-    tensors = {
-        "token_embd.weight": sd["embed_tokens.weight"].data,
-        "output_norm.weight": sd["final_norm_w"].data,
-        "output.weight": sd["lm_head.weight"].data,
-    }
-    for i in range(cfg.num_layers):
-        qkv = sd[f"layers.{i}.attn.qkv_proj.weight"].data
-        gu = sd[f"layers.{i}.mlp.gate_up_proj.weight"].data
-        tensors[f"blk.{i}.attn_q.weight"] = permute(qkv[:q], cfg.num_heads)
-        tensors[f"blk.{i}.attn_k.weight"] = permute(qkv[q:q + kv],
-                                                    cfg.num_kv_heads)
-        tensors[f"blk.{i}.attn_v.weight"] = qkv[q + kv:]
-        tensors[f"blk.{i}.attn_output.weight"] = \
-            sd[f"layers.{i}.attn.o_proj.weight"].data
-        tensors[f"blk.{i}.ffn_gate.weight"] = gu[:inter]
-        tensors[f"blk.{i}.ffn_up.weight"] = gu[inter:]
-        tensors[f"blk.{i}.ffn_down.weight"] = \
-            sd[f"layers.{i}.mlp.down_proj.weight"].data
-        tensors[f"blk.{i}.attn_norm.weight"] = \
-            sd[f"layers.{i}.input_norm_w"].data
-        tensors[f"blk.{i}.ffn_norm.weight"] = \
-            sd[f"layers.{i}.post_norm_w"].data
-    meta = {
-        "general.architecture": "llama",
-        "general.name": cfg.name,
-        "llama.block_count": cfg.num_layers,
-        "llama.embedding_length": cfg.hidden_size,
-        "llama.feed_forward_length": cfg.intermediate_size,
-        "llama.attention.head_count": cfg.num_heads,
-        "llama.attention.head_count_kv": cfg.num_kv_heads,
-        "llama.context_length": cfg.max_position,
-        "llama.rope.freq_base": float(cfg.rope_base),
-    }
-    if quant:
-        proj = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate",
-                "ffn_up", "ffn_down")
-        block = 256 if quant.endswith(("_k", "_k_m")) else 32
-        for name, t in list(tensors.items()):
-            if not (name.startswith("blk.") and name.split(".")[2] in proj
-                    and t.shape[1] % block == 0):
-                continue
-            gtype = quant.upper()
-            if quant == "q4_k_m":
-                # llama.cpp's recipe: Q4_K, with Q6_K for attn_v and
-                # ffn_down in the layers q4_k_m_uses_q6_k selects
-                part, layer = name.split(".")[2], int(name.split(".")[1])
-                more = part in ("attn_v", "ffn_down") and \
-                    g.q4_k_m_uses_q6_k(layer, cfg.num_layers)
-                gtype = "Q6_K" if more else "Q4_K"
-            tensors[name] = g.quantize_ggml(t, gtype)
-        if quant == "q4_k_m":
-            for name, gtype in (("output.weight", "Q6_K"),
-                                ("token_embd.weight", "Q4_K")):
-                if tensors[name].shape[1] % 256 == 0:
-                    tensors[name] = g.quantize_ggml(tensors[name], gtype)
-    g.write_gguf(out, meta, tensors)
+    n = g.export_model_gguf(model, out, quant=quant,
+                            experts_only=experts_only)
     est = g.estimate_gguf_bytes(out)
-    typer.echo(f"wrote {out}: {len(tensors)} tensors, "
+    typer.echo(f"wrote {out}: {n} tensors, "
                f"{est['weights'] >> 20} MiB")
 
 

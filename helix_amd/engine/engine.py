@@ -75,6 +75,9 @@ class EngineConfig:
     # None | "fp8" (e4m3 W8A8) | "q4_0" | "q8_0" | "q4_k" | "q6_k" (ggml
     # weight-only)
     quantization: Optional[str] = None
+    # None | "q4_0" | "q8_0": a mixture of experts' expert weights alone,
+    # quantised after load (ggml blocks, ops/hip/moe_wq.hip)
+    expert_quantization: Optional[str] = None
     kv_cache_dtype: str = "bf16"              # "bf16" | "fp8" (e4m3 KV)
     max_loras: int = 0                        # adapter slots (0 = LoRA off)
     max_lora_rank: int = 16
@@ -94,9 +97,21 @@ class LLMEngine:
         self.tp_size = tp_size
         self.tp_rank = tp_rank
         self.tp_group = tp_group
+        if cfg.expert_quantization is not None:
+            if cfg.expert_quantization not in ("q4_0", "q8_0"):
+                raise ValueError(
+                    f"expert_quantization={cfg.expert_quantization!r}: "
+                    "expected None, 'q4_0' or 'q8_0'")
+            if self.model_cfg.num_experts == 0:
+                raise ValueError(
+                    f"expert_quantization={cfg.expert_quantization!r}: model "
+                    f"{cfg.model!r} is dense and has no experts (use "
+                    "`quantization` for its projections)")
         if self.model_cfg.num_experts > 0:
-            # MoE experts are served in bf16 on one GPU only (docs/KERNELS.md
-            # "moe.hip": out of scope); refuse before allocating anything
+            # MoE experts are served on one GPU only, in bf16 or as Q4_0 /
+            # Q8_0 blocks (expert_quantization); the attention projections
+            # stay bf16 (docs/KERNELS.md "moe_wq.hip": out of scope); refuse
+            # before allocating anything
             bad = [what for what, on in (
                 (f"quantization={cfg.quantization!r}",
                  cfg.quantization is not None),
@@ -105,9 +120,10 @@ class LLMEngine:
             if bad:
                 raise ValueError(
                     f"model {cfg.model!r} is a mixture of experts: "
-                    f"{', '.join(bad)} is not supported (quantised experts, "
-                    "LoRA on experts and tensor-parallel experts are not "
-                    "implemented)")
+                    f"{', '.join(bad)} is not supported (whole-model "
+                    "quantisation, LoRA on experts and tensor-parallel "
+                    "experts are not implemented; expert_quantization="
+                    "'q4_0' | 'q8_0' quantises the experts alone)")
         if model is None:
             dtype = torch.bfloat16
             model = LlamaForCausalLM(self.model_cfg, tp_size, tp_rank)
@@ -122,6 +138,11 @@ class LLMEngine:
             from helix_amd.models.quant import has_wq, quantize_model_wq
             if not has_wq(model):
                 quantize_model_wq(model, cfg.quantization)
+        if cfg.expert_quantization is not None:
+            # experts only, after load; layers whose experts are already
+            # quantised (resident GGUF load) are served as they are
+            from helix_amd.models.quant import quantize_model_experts
+            quantize_model_experts(model, cfg.expert_quantization)
         # a model holding WQLinears (quantized above, or loaded resident
         # from GGUF and perhaps moved since) owns its dequant scratch;
         # a no-op for every other model

@@ -19,7 +19,13 @@ re-encoding) and dequantizes them inside the GEMM:
   * a projection whose parts are each Q4_K or Q6_K becomes a KQLinear with
     one segment per part; the parts may differ in type (a Q4_K_M file's
     qkv_proj is Q4_K, Q4_K, Q6_K). It needs K % 256 == 0 and every part's
-    N % 16 == 0.
+    N % 16 == 0;
+  * a Mixtral layer's experts (merged `ffn_gate_exps` / `ffn_up_exps` /
+    `ffn_down_exps`, or the older per-expert `ffn_gate.{e}` names) whose gate
+    and up are the same one of Q4_0/Q8_0 and whose down is one of them
+    become MoEMLP's quantised planes (ops/hip/moe_wq.hip). The merged
+    layout is ggml's convention as documented; like the K-quant decoders it
+    has not been checked against a file written by llama.cpp.
 Everything else, including any other mix of types (Q4_0 with Q8_0, a
 K-quant part next to a legacy or float part) and Q5_K, is dequantized to
 the model dtype as before. `write_gguf` accepts pre-quantized
@@ -315,7 +321,26 @@ def map_gguf_name(name: str):
         }
         if rest in m:
             return m[rest]
+        # Mixtral experts: the router, the merged [E, rows, K] tensors and
+        # the older one-tensor-per-expert names ("gate_exp:3" = expert 3)
+        moe = {
+            "ffn_gate_inp.weight": (f"layers.{i}.mlp.router_w", None),
+            "ffn_gate_exps.weight": (f"layers.{i}.mlp.w13", "gate_exps"),
+            "ffn_up_exps.weight": (f"layers.{i}.mlp.w13", "up_exps"),
+            "ffn_down_exps.weight": (f"layers.{i}.mlp.w2", "down_exps"),
+        }
+        if rest in moe:
+            return moe[rest]
+        if len(parts) == 5 and parts[4] == "weight" and parts[3].isdigit() \
+                and parts[2] in _EXPERT_PARTS:
+            role, attr = _EXPERT_PARTS[parts[2]]
+            return f"layers.{i}.mlp.{attr}", f"{role}:{parts[3]}"
     return name, None
+
+
+# per-expert legacy tensor `blk.i.<part>.<e>.weight` -> (role, MoEMLP attr)
+_EXPERT_PARTS = {"ffn_gate": ("gate_exp", "w13"), "ffn_up": ("up_exp", "w13"),
+                 "ffn_down": ("down_exp", "w2")}
 
 
 def unpermute_rope(w: torch.Tensor, n_head: int) -> torch.Tensor:
@@ -525,15 +550,95 @@ def _install_resident(model, g: GGUFFile) -> set:
     return used
 
 
+def _expert_tensor_names(g: GGUFFile, i: int, E: int):
+    """[gate names, up names, down names] of layer i's experts: one merged
+    tensor each, or E per-expert tensors each (the older layout); None when
+    the file has neither complete."""
+    merged = [[f"blk.{i}.ffn_{p}_exps.weight"] for p in ("gate", "up", "down")]
+    if all(n[0] in g.tensors for n in merged):
+        return merged
+    legacy = [[f"blk.{i}.ffn_{p}.{e}.weight" for e in range(E)]
+              for p in ("gate", "up", "down")]
+    if all(n in g.tensors for part in legacy for n in part):
+        return legacy
+    return None
+
+
+def _install_resident_experts(model, g: GGUFFile) -> set:
+    """Keep a layer's experts as the file's blocks (MoEMLP's quantised
+    state) when gate and up are the same one of Q4_0/Q8_0 and down is one of
+    Q4_0/Q8_0. Any other mix, K-quant experts included, is left to the
+    dense loader. Returns the GGUF tensor names consumed."""
+    from helix_amd import ops
+    from helix_amd.models.quant import attach_wq_scratch
+    cfg = model.cfg
+    E, H, I = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
+    used = set()
+    if E == 0 or H % 32 or I % 32:
+        return used
+    for i in range(cfg.num_layers):
+        mlp = model.get_submodule(f"layers.{i}.mlp")
+        if getattr(mlp, "expert_fmt", True) is not None:
+            continue                       # no MoEMLP, or already quantised
+        names = _expert_tensor_names(g, i, E)
+        if names is None:
+            continue
+        types = [{g.tensors[n].type_name for n in part} for part in names]
+        if any(len(t) != 1 for t in types):
+            continue
+        tg, tu, td = (next(iter(t)) for t in types)
+        if tg != tu or tg not in _WQ_FMT or td not in _WQ_FMT:
+            continue
+        shapes = [(I, H), (I, H), (H, I)]
+        if any(tuple(g.tensors[n].shape) !=
+               ((E,) + s if len(part) == 1 else s)
+               for part, s in zip(names, shapes) for n in part):
+            continue
+        dev = mlp.router_w.device
+        planes = []
+        for part, (rows, K), t in zip(names, shapes, (tg, tu, td)):
+            fmt = _WQ_FMT[t]
+            # rows are independent: a merged tensor is [E*rows, K]
+            n_rows = E * rows if len(part) == 1 else rows
+            got = [ops.unpack_ggml(g.read_raw(n), (n_rows, K), fmt)
+                   for n in part]
+            planes.append(tuple(
+                torch.cat(ps, dim=0).view(E, rows, -1) for ps in zip(*got)))
+            used.update(part)
+        gate, up, down = planes
+        w13 = tuple(torch.cat([a, b], dim=1).contiguous().to(dev)
+                    for a, b in zip(gate, up))
+        w2 = tuple(p.contiguous().to(dev) for p in down)
+        mlp.set_quantized_experts(w13, w2, (_WQ_FMT[tg], _WQ_FMT[td]))
+    if used:
+        attach_wq_scratch(model)
+    return used
+
+
+def _check_expert_metadata(cfg, g: GGUFFile) -> None:
+    arch = g.arch() or "llama"
+    for key, want in ((f"{arch}.expert_count", cfg.num_experts),
+                      (f"{arch}.expert_used_count", cfg.experts_per_token)):
+        if key in g.metadata and int(g.metadata[key]) != \
+                (want if cfg.num_experts > 0 else 0):
+            raise ValueError(
+                f"{g.path}: {key} = {g.metadata[key]}, but preset "
+                f"{cfg.name!r} has {want if cfg.num_experts > 0 else 0}")
+
+
 @torch.inference_mode()
 def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     """Load a GGUF llama checkpoint into a helix_amd Llama model
     (dequantizing to the model dtype; Q/K rope rows un-permuted). With
-    keep_quantized, Q4_0/Q8_0 projections (WQLinear) and Q4_K/Q6_K
-    projections (KQLinear) stay resident as the file's blocks; see the
-    module docstring."""
+    keep_quantized, Q4_0/Q8_0 projections (WQLinear), Q4_K/Q6_K
+    projections (KQLinear) and Q4_0/Q8_0 experts (MoEMLP's planes) stay
+    resident as the file's blocks; see the module docstring. A file whose
+    expert_count / expert_used_count differ from the model's is refused."""
     g = GGUFFile(path)
+    _check_expert_metadata(model.cfg, g)
     resident = _install_resident(model, g) if keep_quantized else set()
+    if keep_quantized:
+        resident |= _install_resident_experts(model, g)
     params = dict(model.named_parameters())
     cfg = model.cfg
     q, kv = cfg.q_size, cfg.kv_size
@@ -562,7 +667,131 @@ def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
             p.data[:inter].copy_(t)
         elif role == "up":
             p.data[inter:].copy_(t)
+        elif role == "gate_exps":               # merged [E, I, H]
+            p.data[:, :inter].copy_(t)
+        elif role == "up_exps":
+            p.data[:, inter:].copy_(t)
+        elif role is not None and ":" in role:  # one expert's tensor
+            kind, e = role.split(":")
+            if kind == "gate_exp":
+                p.data[int(e), :inter].copy_(t)
+            elif kind == "up_exp":
+                p.data[int(e), inter:].copy_(t)
+            else:
+                p.data[int(e)].copy_(t)
         else:
             p.data.copy_(t)
         loaded += 1
     return loaded
+
+
+# -- export (`helix export-gguf`) ---------------------------------------
+
+EXPORT_QUANTS = ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m")
+
+
+def export_model_gguf(model, path: str, quant: str = "",
+                      experts_only: bool = False) -> int:
+    """Write `model` (a dense LlamaForCausalLM, experts in bf16 if it has
+    any) as a GGUF v3 checkpoint with llama.cpp tensor names, Q/K rows
+    permuted for GGML rope. `quant` quantizes the projection weights (norms
+    and embeddings stay as they are) as `helix export-gguf --quant` says.
+    A mixture of experts writes the router, the merged ffn_*_exps tensors
+    ([E, rows, K]) and llama.expert_count / expert_used_count; q4_0 / q8_0
+    quantize the experts too (quantize_ggml on the flattened rows), the
+    K-quant flags leave them bf16. experts_only: quantize nothing but the
+    experts. Returns the number of tensors written."""
+    if quant not in EXPORT_QUANTS:
+        raise ValueError(f"quant must be one of {EXPORT_QUANTS[1:]}")
+    cfg = model.cfg
+
+    def permute(w, n_head):
+        o, i = w.shape
+        return (w.reshape(n_head, 2, o // n_head // 2, i)
+                .swapaxes(1, 2).reshape(o, i))
+
+    sd = dict(model.named_parameters())
+    q, kv, inter = cfg.q_size, cfg.kv_size, cfg.intermediate_size
+    moe = cfg.num_experts > 0
+    tensors = {
+        "token_embd.weight": sd["embed_tokens.weight"].data,
+        "output_norm.weight": sd["final_norm_w"].data,
+        "output.weight": sd["lm_head.weight"].data,
+    }
+    for i in range(cfg.num_layers):
+        qkv = sd[f"layers.{i}.attn.qkv_proj.weight"].data
+        tensors[f"blk.{i}.attn_q.weight"] = permute(qkv[:q], cfg.num_heads)
+        tensors[f"blk.{i}.attn_k.weight"] = permute(qkv[q:q + kv],
+                                                    cfg.num_kv_heads)
+        tensors[f"blk.{i}.attn_v.weight"] = qkv[q + kv:]
+        tensors[f"blk.{i}.attn_output.weight"] = \
+            sd[f"layers.{i}.attn.o_proj.weight"].data
+        if moe:
+            if f"layers.{i}.mlp.w13" not in sd:
+                raise ValueError("export_model_gguf: the experts of layer "
+                                 f"{i} are already quantised")
+            w13 = sd[f"layers.{i}.mlp.w13"].data
+            tensors[f"blk.{i}.ffn_gate_inp.weight"] = \
+                sd[f"layers.{i}.mlp.router_w"].data
+            tensors[f"blk.{i}.ffn_gate_exps.weight"] = w13[:, :inter]
+            tensors[f"blk.{i}.ffn_up_exps.weight"] = w13[:, inter:]
+            tensors[f"blk.{i}.ffn_down_exps.weight"] = \
+                sd[f"layers.{i}.mlp.w2"].data
+        else:
+            gu = sd[f"layers.{i}.mlp.gate_up_proj.weight"].data
+            tensors[f"blk.{i}.ffn_gate.weight"] = gu[:inter]
+            tensors[f"blk.{i}.ffn_up.weight"] = gu[inter:]
+            tensors[f"blk.{i}.ffn_down.weight"] = \
+                sd[f"layers.{i}.mlp.down_proj.weight"].data
+        tensors[f"blk.{i}.attn_norm.weight"] = \
+            sd[f"layers.{i}.input_norm_w"].data
+        tensors[f"blk.{i}.ffn_norm.weight"] = \
+            sd[f"layers.{i}.post_norm_w"].data
+    meta = {
+        "general.architecture": "llama",
+        "general.name": cfg.name,
+        "llama.block_count": cfg.num_layers,
+        "llama.embedding_length": cfg.hidden_size,
+        "llama.feed_forward_length": cfg.intermediate_size,
+        "llama.attention.head_count": cfg.num_heads,
+        "llama.attention.head_count_kv": cfg.num_kv_heads,
+        "llama.context_length": cfg.max_position,
+        "llama.rope.freq_base": float(cfg.rope_base),
+    }
+    if moe:
+        meta["llama.expert_count"] = cfg.num_experts
+        meta["llama.expert_used_count"] = cfg.experts_per_token
+    if quant:
+        proj = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate",
+                "ffn_up", "ffn_down")
+        exps = ("ffn_gate_exps", "ffn_up_exps", "ffn_down_exps")
+        block = 256 if quant.endswith(("_k", "_k_m")) else 32
+        for name, t in list(tensors.items()):
+            part = name.split(".")[2] if name.startswith("blk.") else ""
+            if part in exps:
+                # [E, rows, K]: rows are independent, so quantize the
+                # flattened rows and keep the 3-D shape
+                if block == 32 and t.shape[2] % 32 == 0:
+                    qt = quantize_ggml(t.reshape(-1, t.shape[2]),
+                                       quant.upper())
+                    tensors[name] = GGMLQuantized(qt.raw, tuple(t.shape),
+                                                  qt.type_name)
+                continue
+            if experts_only or part not in proj or t.shape[1] % block:
+                continue
+            gtype = quant.upper()
+            if quant == "q4_k_m":
+                # llama.cpp's recipe: Q4_K, with Q6_K for attn_v and
+                # ffn_down in the layers q4_k_m_uses_q6_k selects
+                layer = int(name.split(".")[1])
+                more = part in ("attn_v", "ffn_down") and \
+                    q4_k_m_uses_q6_k(layer, cfg.num_layers)
+                gtype = "Q6_K" if more else "Q4_K"
+            tensors[name] = quantize_ggml(t, gtype)
+        if quant == "q4_k_m" and not experts_only:
+            for name, gtype in (("output.weight", "Q6_K"),
+                                ("token_embd.weight", "Q4_K")):
+                if tensors[name].shape[1] % 256 == 0:
+                    tensors[name] = quantize_ggml(tensors[name], gtype)
+    write_gguf(path, meta, tensors)
+    return len(tensors)

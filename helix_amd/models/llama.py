@@ -249,12 +249,23 @@ class MoEMLP(nn.Module):
     `experts_per_token` of them per token (ops.moe_forward). The weights are
     plain Parameters, not nn.Linear, so the quantisers' and the LoRA
     manager's nn.Linear walks never see them; expert weights are neither
-    quantised, adapted nor sharded."""
+    adapted nor sharded.
+
+    Quantised state (set_quantized_experts; models/quant.py
+    quantize_model_experts or a resident GGUF load): the bf16 `w13` / `w2`
+    Parameters are deleted and the experts live as ggml Q4_0/Q8_0 planes in
+    the buffers `w13_qs`, `w13_d`, `w2_qs`, `w2_d`, with `expert_fmt` the
+    (w13 format, w2 format) pair; forward runs ops.moe_forward_wq. The
+    router stays a bf16 F.linear. `scratch` is the model's dequant buffer
+    for the eager library prefill path (quant.attach_wq_scratch)."""
 
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         e, h, i = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
         self.k = cfg.experts_per_token
+        self.num_experts, self.hidden_size, self.intermediate_size = e, h, i
+        self.expert_fmt = None
+        self.scratch = None
         # created in bf16, the one dtype the kernels serve: mixtral-8x7b's
         # 45 G expert weights never exist in fp32, on the host or the GPU
         bf16 = torch.bfloat16
@@ -267,8 +278,58 @@ class MoEMLP(nn.Module):
         router_logits = F.linear(x, self.router_w)
         # decode runs under hipGraph capture: always the fused kernels there
         fused = True if not getattr(meta, "is_prefill", True) else None
+        if self.expert_fmt is not None:
+            return ops.moe_forward_wq(x, router_logits,
+                                      (self.w13_qs, self.w13_d),
+                                      (self.w2_qs, self.w2_d),
+                                      self.expert_fmt, self.k, fused=fused,
+                                      scratch=self.scratch)
         return ops.moe_forward(x, router_logits, self.w13, self.w2, self.k,
                                fused=fused)
+
+    def set_quantized_experts(self, w13_planes, w2_planes, fmt) -> None:
+        """Replace the bf16 experts by (qs, d) planes of the given format
+        ("q4_0" / "q8_0", or a (w13, w2) pair). Shapes are checked against
+        the config; the bf16 Parameters are deleted."""
+        f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
+        e, h, i = self.num_experts, self.hidden_size, self.intermediate_size
+        for name, (qs, d), f, rows, k in (
+                ("w13", w13_planes, f13, 2 * i, h),
+                ("w2", w2_planes, f2, h, i)):
+            bits = ops.wq_bits(f)
+            qdt = torch.uint8 if bits == 4 else torch.int8
+            qshape = (e, rows, k // 2 if bits == 4 else k)
+            if qs.dtype != qdt or tuple(qs.shape) != qshape \
+                    or d.dtype != torch.float16 \
+                    or tuple(d.shape) != (e, rows, k // 32):
+                raise ValueError(
+                    f"MoEMLP: {name} {f} planes are {qs.dtype} "
+                    f"{tuple(qs.shape)} / {d.dtype} {tuple(d.shape)}, "
+                    f"expected {qdt} {qshape} / fp16 {(e, rows, k // 32)}")
+        for name in ("w13", "w2"):
+            if name in self._parameters:
+                del self._parameters[name]
+        for name, t in (("w13_qs", w13_planes[0]), ("w13_d", w13_planes[1]),
+                        ("w2_qs", w2_planes[0]), ("w2_d", w2_planes[1])):
+            self._buffers.pop(name, None)
+            self.register_buffer(name, t.contiguous(), persistent=True)
+        self.expert_fmt = (f13, f2)
+
+    def _apply(self, fn, recurse=True):
+        # as WQLinear._apply: the block scales are fp16 by format and follow
+        # the device only under model.to(dtype); a scratch left on another
+        # device is dropped (attach_wq_scratch gives the model a new one)
+        if self.expert_fmt is None:
+            return super()._apply(fn, recurse)
+        keep = {n: self._buffers[n] for n in ("w13_d", "w2_d")}
+        super()._apply(fn, recurse)
+        for n, b in keep.items():
+            if self._buffers[n].dtype != torch.float16:
+                self._buffers[n] = b.to(self._buffers[n].device)
+        if self.scratch is not None \
+                and self.scratch.device != self.w13_qs.device:
+            self.scratch = None
+        return self
 
 
 class DecoderLayer(nn.Module):

@@ -248,22 +248,37 @@ class KQLinear(nn.Module):
         return out.reshape(*shape, N)
 
 
+def _is_wq_moe(m: nn.Module) -> bool:
+    """A models/llama.py MoEMLP in its quantised state."""
+    return getattr(m, "expert_fmt", None) is not None
+
+
+def _wq_device(m: nn.Module):
+    return m.w13_qs.device if _is_wq_moe(m) else m.device
+
+
 def attach_wq_scratch(model: nn.Module) -> None:
     """Give `model` its own dequant buffer: one bf16 tensor per GPU it has
-    WQLinears or KQLinears on, sized for the largest of them and shared by
-    them alone.
+    WQLinears, KQLinears or quantised MoEMLPs on, sized for the largest of
+    them and shared by them alone.
     Called when the weights are installed and again by the engine if the
     model was moved since; never from a forward. A model whose modules
     already hold a fitting buffer is left as it is (captured graphs point
     into it)."""
     mods = [m for m in model.modules()
-            if isinstance(m, (WQLinear, KQLinear)) and m.device.type == "cuda"]
+            if (isinstance(m, (WQLinear, KQLinear)) or _is_wq_moe(m))
+            and _wq_device(m).type == "cuda"]
     need: dict = {}
     for m in mods:
-        n = m.in_features * m.out_features
-        need[m.device] = max(need.get(m.device, 0), n)
+        if _is_wq_moe(m):
+            # the library prefill path dequantizes one expert's w13, the
+            # larger of its two weights: 2*I*H elements
+            n = 2 * m.intermediate_size * m.hidden_size
+        else:
+            n = m.in_features * m.out_features
+        need[_wq_device(m)] = max(need.get(_wq_device(m), 0), n)
     for dev, numel in need.items():
-        mine = [m for m in mods if m.device == dev]
+        mine = [m for m in mods if _wq_device(m) == dev]
         cur = mine[0].scratch
         if cur is not None and cur.device == dev and cur.numel() >= numel \
                 and all(m.scratch is cur for m in mine):
@@ -301,5 +316,32 @@ def quantize_model_wq(model: nn.Module, fmt: str,
     return converted
 
 
+def quantize_model_experts(model: nn.Module, fmt: str) -> int:
+    """Quantise the experts of every bf16 MoEMLP to ggml Q4_0/Q8_0 planes
+    with ggml's reference quantizer (rows are independent, so a stack is
+    quantize_wq on its [E*rows, K] view), layer by layer: a layer's bf16
+    experts are freed before the next layer is touched. The router and
+    everything outside the experts are left alone. Returns the number of
+    layers converted; a layer already quantised is skipped."""
+    from helix_amd.models.llama import MoEMLP
+    ops.wq_bits(fmt)
+    converted = 0
+    for m in model.modules():
+        if not isinstance(m, MoEMLP) or m.expert_fmt is not None:
+            continue
+        planes = []
+        for name in ("w13", "w2"):
+            w = getattr(m, name).data
+            E, rows, K = w.shape
+            qs, d = ops.quantize_wq(w.view(E * rows, K), fmt)
+            planes.append((qs.view(E, rows, -1), d.view(E, rows, K // 32)))
+            del w
+        m.set_quantized_experts(planes[0], planes[1], fmt)
+        converted += 1
+    attach_wq_scratch(model)
+    return converted
+
+
 def has_wq(model: nn.Module) -> bool:
-    return any(isinstance(m, (WQLinear, KQLinear)) for m in model.modules())
+    return any(isinstance(m, (WQLinear, KQLinear)) or _is_wq_moe(m)
+               for m in model.modules())

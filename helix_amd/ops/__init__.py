@@ -622,6 +622,134 @@ def moe_forward(x: torch.Tensor, router_logits: torch.Tensor,
     return moe_experts(x, w13, w2, ids, w, fused=fused)
 
 
+# -- routed expert GEMMs over Q4_0 / Q8_0 experts (ops/hip/moe_wq.hip) --
+# Largest T at which moe_experts_wq(fused=None) takes the fused kernels.
+# MOE_FUSED_MAX_T's rule: the largest benchmarked T at which the fused path
+# is not slower than this feature's own library path (which pays a
+# dequantise per non-empty expert) on uniform routing, in two runs of
+# scripts/bench_moe.py --fmt q4_0 / q8_0; the smaller of the two formats.
+# MEASURED, not the placeholder (profiles/r09_moe_wq.md): both formats give
+# 128. Fused over library on uniform routing, q4_0 / q8_0: 4.9x / 4.2x at
+# T = 1, 3.6x / 3.4x at 64, 2.5x / 2.2x at 128 and 0.86x / 0.80x at 512, in
+# both runs. The value equals the bf16 one, the margin at 128 does not: the
+# library path pays a dequantise per expert, and between 128 and 512 no T
+# was benchmarked.
+MOE_WQ_FUSED_MAX_T = 128
+
+
+def _moe_fmt_pair(fmt):
+    f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
+    wq_bits(f13), wq_bits(f2)
+    return f13, f2
+
+
+def dequantize_experts_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
+                          dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Expert stack planes [E, rows, ...] -> [E, rows, K] with the torch
+    reference (rows are independent, so it is dequantize_wq on E*rows
+    rows): d*q in fp32, one rounding to `dtype`."""
+    E, rows, nblk = d.shape
+    w = dequantize_wq(qs.reshape(E * rows, -1), d.reshape(E * rows, nblk),
+                      fmt, dtype)
+    return w.view(E, rows, nblk * 32)
+
+
+def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
+                   topk_ids: torch.Tensor, topk_w: torch.Tensor,
+                   fused: bool | None = None, out: torch.Tensor | None = None,
+                   act: torch.Tensor | None = None,
+                   ypair: torch.Tensor | None = None,
+                   scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """moe_experts over experts kept as ggml Q4_0/Q8_0 planes.
+    w13_planes = (qs [E, 2I, H/2 or H], d fp16 [E, 2I, H/32]), w2_planes =
+    (qs [E, H, I/2 or I], d fp16 [E, H, I/32]); `fmt` is "q4_0" / "q8_0" or
+    a (w13 format, w2 format) pair.
+    GPU, fused=True: moe_align + the two dequant-fused routed GEMM kernels +
+    moe_combine; capture-safe, any T. GPU, fused=False: the eager library
+    path (one host sync): per non-empty expert dequant_wq of w13[e] into
+    `scratch`, F.linear, silu_and_mul, dequant_wq of w2[e] into the same
+    scratch (same stream, so ordered), F.linear; scaled into the same fp32
+    ypair, the same moe_combine. `scratch` is a contiguous bf16 buffer of at
+    least 2*I*H elements, allocated per call when None. fused=None: fused
+    up to MOE_WQ_FUSED_MAX_T tokens.
+    CPU: moe_experts (the torch reference) on the stacks dequantised to
+    bf16, the definition."""
+    f13, f2 = _moe_fmt_pair(fmt)
+    q13, d13 = w13_planes
+    q2, d2 = w2_planes
+    if not x.is_cuda:
+        return ref.moe_experts(x, dequantize_experts_wq(q13, d13, f13),
+                               dequantize_experts_wq(q2, d2, f2),
+                               topk_ids, topk_w)
+    if x.dim() != 2 or topk_ids.dim() != 2:
+        raise ValueError("moe_experts_wq: x must be [T, H] and topk_ids "
+                         "[T, k]")
+    if d13.dim() != 3 or d2.dim() != 3:
+        raise ValueError("moe_experts_wq: scale planes must be 3-D")
+    T, k = topk_ids.shape
+    E, I, H = d13.shape[0], d13.shape[1] // 2, d13.shape[2] * 32
+    P = T * k
+    if x.shape[0] != T or tuple(topk_w.shape) != (T, k):
+        raise ValueError(
+            f"moe_experts_wq: x {tuple(x.shape)}, topk_ids "
+            f"{tuple(topk_ids.shape)} and topk_w {tuple(topk_w.shape)} "
+            f"disagree on [T, k]")
+    if fused is None:
+        fused = T <= MOE_WQ_FUSED_MAX_T
+    if act is None:
+        act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
+    if ypair is None:
+        ypair = torch.empty(P, H, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(T, H, dtype=torch.bfloat16, device=x.device)
+    C = _native()
+    off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
+    pairs = torch.empty(P, dtype=torch.int32, device=x.device)
+    C.moe_align(off, pairs, topk_ids, E)
+    if fused:
+        C.moe_gemm_gated_wq(act, x, q13, d13, wq_bits(f13), off, pairs, k)
+        C.moe_gemm_down_wq(ypair, act, q2, d2, wq_bits(f2), topk_w, off,
+                           pairs)
+    else:
+        if x.dtype != torch.bfloat16:
+            raise ValueError("moe_experts_wq: x must be bf16 on GPU")
+        if tuple(d2.shape) != (E, H, I // 32) or x.shape[1] != H \
+                or tuple(act.shape) != (P, I) or tuple(ypair.shape) != (P, H) \
+                or ypair.dtype != torch.float32:
+            raise ValueError("moe_experts_wq: shape mismatch between x, the "
+                             "planes, act and ypair")
+        if scratch is None:
+            scratch = torch.empty(2 * I * H, dtype=torch.bfloat16,
+                                  device=x.device)
+        offs = off.tolist()                       # the one host sync
+        rows = pairs[:offs[E]].long()
+        xg = x[rows // k]
+        tw = topk_w.reshape(-1)[rows]
+        for e in range(E):
+            lo, hi = offs[e], offs[e + 1]
+            if hi == lo:
+                continue
+            w = dequant_wq(q13[e], d13[e], f13, out=scratch)
+            a = silu_and_mul(torch.nn.functional.linear(xg[lo:hi], w))
+            act[rows[lo:hi]] = a
+            w = dequant_wq(q2[e], d2[e], f2, out=scratch)
+            y = torch.nn.functional.linear(a, w)
+            ypair[rows[lo:hi]] = y.float() * tw[lo:hi, None]
+    C.moe_combine(out, ypair, k)
+    return out
+
+
+def moe_forward_wq(x: torch.Tensor, router_logits: torch.Tensor,
+                   w13_planes, w2_planes, fmt, k: int,
+                   fused: bool | None = None,
+                   scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """One MoE MLP over quantised experts: route (moe_route) and run the
+    routed experts (moe_experts_wq)."""
+    ids, w = moe_route(router_logits, k)
+    return moe_experts_wq(x, w13_planes, w2_planes, fmt, ids, w, fused=fused,
+                          scratch=scratch)
+
+
 def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)

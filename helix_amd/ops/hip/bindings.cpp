@@ -82,6 +82,14 @@ void moe_gemm_down(torch::Tensor ypair, torch::Tensor act, torch::Tensor w2,
                    torch::Tensor topk_w, torch::Tensor expert_off,
                    torch::Tensor sorted_pairs);
 void moe_combine(torch::Tensor out, torch::Tensor ypair, int64_t k);
+void moe_gemm_gated_wq(torch::Tensor act, torch::Tensor x,
+                       torch::Tensor w13_qs, torch::Tensor w13_d, int64_t bits,
+                       torch::Tensor expert_off, torch::Tensor sorted_pairs,
+                       int64_t k);
+void moe_gemm_down_wq(torch::Tensor ypair, torch::Tensor act,
+                      torch::Tensor w2_qs, torch::Tensor w2_d, int64_t bits,
+                      torch::Tensor topk_w, torch::Tensor expert_off,
+                      torch::Tensor sorted_pairs);
 int64_t moe_waves(int64_t N, int64_t K, bool gated);
 int64_t moe_max_experts();
 int64_t moe_max_topk();
@@ -150,6 +158,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Routed expert GEMM 2: ypair[p] = topk_w[p] * (act[p] @ w2_e^T), fp32");
   m.def("moe_combine", &moe_combine,
         "out[t] = bf16(sum over slots of ypair[t*k + j]), fixed order");
+  m.def("moe_gemm_gated_wq", &moe_gemm_gated_wq,
+        "Routed expert GEMM 1 over Q4_0/Q8_0 expert planes, dequant fused "
+        "into the MFMA loop");
+  m.def("moe_gemm_down_wq", &moe_gemm_down_wq,
+        "Routed expert GEMM 2 over Q4_0/Q8_0 expert planes, fp32 ypair");
   m.def("moe_waves", &moe_waves,
         "K-split factor (waves per workgroup) moe_gemm uses for one expert's "
         "[N, K] weight");

@@ -26,6 +26,7 @@ def apply_profile(service: RunnerService, profile: dict) -> dict:
             kv_cache_blocks=m.get("kv_cache_blocks"),
             tp=int(m.get("tp", 1)),
             quantization=m.get("quantization"),
+            expert_quantization=m.get("expert_quantization"),
             kv_cache_dtype=m.get("kv_cache_dtype", "bf16"),
             max_loras=int(m.get("max_loras", 0)),
             max_lora_rank=int(m.get("max_lora_rank", 16)),

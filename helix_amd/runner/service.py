@@ -42,6 +42,8 @@ class ModelSpec:
     # None | "fp8" (W8A8) | "q4_0" | "q8_0" | "q4_k" | "q6_k" (ggml
     # weight-only)
     quantization: Optional[str] = None
+    # None | "q4_0" | "q8_0": a mixture of experts' expert weights alone
+    expert_quantization: Optional[str] = None
     kv_cache_dtype: str = "bf16"
     max_loras: int = 0                 # LoRA adapter slots (0 = off)
     max_lora_rank: int = 16
@@ -104,8 +106,13 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
     cfg = LLAMA_PRESETS[spec.preset]
     emb = cfg.vocab_size * cfg.hidden_size * (1 if cfg.tie_embeddings else 2)
     mlp = 3 * cfg.hidden_size * cfg.intermediate_size
+    experts = 0                     # expert weights held as ggml blocks
     if cfg.num_experts > 0:         # E experts + the [E, H] router
-        mlp = cfg.num_experts * (mlp + cfg.hidden_size)
+        if spec.expert_quantization in ("q4_0", "q8_0"):
+            experts = cfg.num_experts * mlp
+            mlp = cfg.num_experts * cfg.hidden_size
+        else:
+            mlp = cfg.num_experts * (mlp + cfg.hidden_size)
     per_layer = (cfg.hidden_size * (cfg.q_size + 2 * cfg.kv_size)  # qkv
                  + cfg.q_size * cfg.hidden_size                     # o
                  + mlp)
@@ -120,6 +127,12 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
         # kernel's cutoff: one buffer the size of its largest projection
         weights += 2 * max(cfg.hidden_size * (cfg.q_size + 2 * cfg.kv_size),
                            2 * cfg.hidden_size * cfg.intermediate_size)
+    if experts:
+        # quantised experts: 8 x 18 / 8 x 34 bytes per 256 weights, plus the
+        # model's bf16 scratch for one dequantised w13 (2*I*H elements)
+        ebytes = {"q4_0": 144, "q8_0": 272}[spec.expert_quantization]
+        weights += ebytes * (cfg.num_layers * experts) // 256
+        weights += 2 * 2 * cfg.intermediate_size * cfg.hidden_size
     kv_block = 2 * cfg.num_layers * cfg.num_kv_heads * block_size * \
         cfg.head_dim * 2
     if spec.kv_cache_blocks:
@@ -153,6 +166,7 @@ class LLMInstance:
                          max_num_seqs=spec.max_num_seqs,
                          kv_cache_blocks=kv_blocks,
                          quantization=spec.quantization,
+                         expert_quantization=spec.expert_quantization,
                          kv_cache_dtype=spec.kv_cache_dtype,
                          max_loras=spec.max_loras,
                          max_lora_rank=spec.max_lora_rank),

@@ -973,6 +973,7 @@ def create_app(cfg: Optional[ServerConfig] = None,
                 kv_cache_blocks=b.get("kv_cache_blocks"),
                 tp=int(b.get("tp", 1)),
                 quantization=b.get("quantization"),
+                expert_quantization=b.get("expert_quantization"),
                 kv_cache_dtype=b.get("kv_cache_dtype", "bf16"),
                 max_loras=int(b.get("max_loras", 0)),
                 max_lora_rank=int(b.get("max_lora_rank", 16)),

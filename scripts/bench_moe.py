@@ -18,6 +18,13 @@ copies of the layer's weights (more than the 256 MiB last-level cache
 between two uses of a weight), as consecutive layers of a model would. The
 library path's host sync is inside its window: it is part of that path.
 
+--fmt q4_0 | q8_0 times ops.moe_forward_wq on the same layer held as ggml
+Q4_0 / Q8_0 planes (random payload bytes and scales: the time does not
+depend on the values); its library path is the feature's own, with a
+dequantise per non-empty expert. weight_bytes then counts the blocks
+(18 / 34 bytes per 32 weights). Run bf16 and the quantised formats in one
+session to compare them.
+
 A GPU is required; there is no CPU fallback. Run under a time limit, e.g.
     timeout 600 python scripts/bench_moe.py --out moe.jsonl
 """
@@ -47,6 +54,7 @@ def main():
     ap.add_argument("--t", type=int, action="append")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--fmt", default="bf16", choices=("bf16", "q4_0", "q8_0"))
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -54,13 +62,30 @@ def main():
     assert ops.have_native(), "native extension is not built"
     dev = torch.device("cuda:0")
     E, k, H, I = args.experts, args.topk, args.hidden, args.inter
-    expert_bytes = 3 * H * I * 2
+    fmt = args.fmt
+    blk_bytes = {"bf16": 64, "q4_0": 18, "q8_0": 34}[fmt]   # per 32 weights
+    expert_bytes = 3 * H * I * blk_bytes // 32
     # the least a call activates is k experts; keep two uses of a weight
     # more than the last-level cache apart
     copies = max(2, -(-CACHE_BYTES // (k * expert_bytes)))
     g = torch.Generator(device=dev).manual_seed(E + H + I)
     layers = []
+
+    def planes(rows, K, std):
+        # d * q with q uniform over the format's range has about this std
+        qdt, per, qstd = (torch.uint8, K // 2, 4.6) if fmt == "q4_0" \
+            else (torch.int8, K, 73.9)
+        qs = torch.randint(0, 256, (E, rows, per), dtype=torch.uint8,
+                           device=dev, generator=g).view(qdt)
+        d = torch.empty(E, rows, K // 32, device=dev)
+        d.uniform_(0.5, 1.5, generator=g)
+        return qs, (d * (std / qstd)).to(torch.float16)
+
     for _ in range(copies):
+        if fmt != "bf16":
+            layers.append((planes(2 * I, H, H ** -0.5),
+                           planes(H, I, I ** -0.5)))
+            continue
         w13 = torch.empty(E, 2 * I, H, dtype=torch.bfloat16, device=dev)
         w2 = torch.empty(E, H, I, dtype=torch.bfloat16, device=dev)
         w13.normal_(0.0, H ** -0.5, generator=g)
@@ -69,8 +94,12 @@ def main():
 
     def call(fused, x, logits, i):
         w13, w2 = layers[i % copies]
+        if fmt != "bf16":
+            return ops.moe_forward_wq(x, logits, w13, w2, fmt, k, fused=fused,
+                                      scratch=scratch)
         return ops.moe_forward(x, logits, w13, w2, k, fused=fused)
 
+    scratch = torch.empty(2 * I * H, dtype=torch.bfloat16, device=dev)
     lines = []
     for T in args.t or TS:
         for routing in ROUTINGS:
@@ -107,7 +136,7 @@ def main():
             lib_med = statistics.median(times["library"])
             for name, ts in times.items():
                 med, mn = statistics.median(ts), min(ts)
-                rec = {"E": E, "k": k, "H": H, "I": I, "T": T,
+                rec = {"fmt": fmt, "E": E, "k": k, "H": H, "I": I, "T": T,
                        "routing": routing, "path": name,
                        "us_median": round(med, 1), "us_min": round(mn, 1),
                        "distinct_experts": distinct,

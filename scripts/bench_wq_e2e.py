@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """End-to-end decode rate and resident weight bytes of one engine
 configuration: --model, --batch (= max_num_seqs, all slots busy) and
---quant in {none, q8_0, q4_0}. Prints one JSON line.
+--quant in {none, q8_0, q4_0}; a mixture-of-experts preset takes
+--expert-quant in {none, q8_0, q4_0} instead (its experts alone are
+quantised). Prints one JSON line.
 
 One configuration per process, so every run starts from a cold allocator
 and can carry its own time limit:
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--quant", default="none",
                     choices=["none", "q8_0", "q4_0"])
+    ap.add_argument("--expert-quant", default="none",
+                    choices=["none", "q8_0", "q4_0"])
     ap.add_argument("--prompt-len", type=int, default=32)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
@@ -41,7 +45,9 @@ def main():
     cfg = EngineConfig(
         model=args.model, max_num_seqs=args.batch, max_model_len=max_len,
         kv_cache_blocks=args.batch * (max_len // 16 + 2), eos_token_id=-1,
-        quantization=None if args.quant == "none" else args.quant)
+        quantization=None if args.quant == "none" else args.quant,
+        expert_quantization=None if args.expert_quant == "none"
+        else args.expert_quant)
     eng = LLMEngine(cfg, device="cuda:0")
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -65,6 +71,7 @@ def main():
     dt = time.monotonic() - t0
     print(json.dumps({
         "model": args.model, "batch": args.batch, "quant": args.quant,
+        "expert_quant": args.expert_quant,
         "tok_per_s": round(args.batch * args.steps / dt, 1),
         "ms_per_step": round(dt / args.steps * 1e3, 3),
         "model_bytes": model_bytes,
