@@ -497,7 +497,9 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
                     "tensors alone")):
     """Export a model as a GGUF v3 checkpoint (llama.cpp tensor names,
     Q/K rows permuted for GGML rope — interops with the llama.cpp
-    ecosystem; see engine/gguf.py)."""
+    ecosystem; see engine/gguf.py). A Qwen3 preset is written as
+    architecture qwen3 / qwen3moe with its QK-norm tensors and Q/K rows
+    left in place."""
     if quant not in ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m"):
         raise typer.BadParameter(
             "--quant must be q4_0, q8_0, q4_k, q6_k or q4_k_m")

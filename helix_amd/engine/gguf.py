@@ -26,6 +26,14 @@ re-encoding) and dequantizes them inside the GEMM:
     become MoEMLP's quantised planes (ops/hip/moe_wq.hip). The merged
     layout is ggml's convention as documented; like the K-quant decoders it
     has not been checked against a file written by llama.cpp.
+Qwen3 (`general.architecture` qwen3 / qwen3moe): the per-head QK-norm
+weights `attn_q_norm` / `attn_k_norm` load as tensors, and Q/K rows are taken
+as they are: llama.cpp's converter permutes Q/K only for the llama
+architecture, Qwen uses neox (rotate-half) rope. A dense Qwen3 Q4_K_M file
+keeps its projections resident like a Llama one; a qwen3moe file keeps
+Q4_0/Q8_0 experts resident, and K-quant experts (what a Q4_K_M qwen3moe file
+holds) have no routed kernel and are dequantized to bf16. `qwen2` files are
+still un-permuted like llama ones (an open point, docs/PARITY.md).
 Everything else, including any other mix of types (Q4_0 with Q8_0, a
 K-quant part next to a legacy or float part) and Q5_K, is dequantized to
 the model dtype as before. `write_gguf` accepts pre-quantized
@@ -314,6 +322,8 @@ def map_gguf_name(name: str):
             "attn_k.weight": (f"layers.{i}.attn.qkv_proj.weight", "k"),
             "attn_v.weight": (f"layers.{i}.attn.qkv_proj.weight", "v"),
             "attn_output.weight": (f"layers.{i}.attn.o_proj.weight", None),
+            "attn_q_norm.weight": (f"layers.{i}.attn.q_norm_w", None),
+            "attn_k_norm.weight": (f"layers.{i}.attn.k_norm_w", None),
             "ffn_gate.weight": (f"layers.{i}.mlp.gate_up_proj.weight",
                                 "gate"),
             "ffn_up.weight": (f"layers.{i}.mlp.gate_up_proj.weight", "up"),
@@ -357,6 +367,15 @@ def unpermute_rope(w: torch.Tensor, n_head: int) -> torch.Tensor:
             .swapaxes(1, 2).reshape(out, inp))
 
 
+# architectures whose Q/K rows llama.cpp's converter leaves in HF order
+# (neox rope): nothing to un-permute on load, nothing to permute on export
+_NEOX_ARCHS = ("qwen3", "qwen3moe")
+
+
+def _rows_permuted(arch: Optional[str]) -> bool:
+    return (arch or "llama") not in _NEOX_ARCHS
+
+
 # -- estimation (reference estimate.go role) ---------------------------
 
 def estimate_gguf_bytes(path: str, kv_tokens: int = 0,
@@ -373,7 +392,9 @@ def estimate_gguf_bytes(path: str, kv_tokens: int = 0,
         g.metadata.get(f"{arch}.attention.head_count", 0)))
     n_embd = int(g.metadata.get(f"{arch}.embedding_length", 0))
     n_head = int(g.metadata.get(f"{arch}.attention.head_count", 1))
-    head_dim = n_embd // max(1, n_head)
+    # Qwen3's head_dim is not n_embd / n_head; such files say so
+    head_dim = int(g.metadata.get(f"{arch}.attention.key_length",
+                                  n_embd // max(1, n_head)))
     kv = 2 * n_layer * n_kv_head * head_dim * kv_tokens * kv_dtype_bytes
     return {"weights": weights, "kv": kv, "total": weights + kv}
 
@@ -518,6 +539,7 @@ def _install_resident(model, g: GGUFFile) -> set:
         return set()
     dev = todo[0][2].weight.device
     used = set()
+    permuted = _rows_permuted(g.arch())
     for owner, attr, lin, names, parts, fmts in todo:
         kq = fmts[0] in _KQ_FMT.values()
         plane_parts = []
@@ -527,7 +549,7 @@ def _install_resident(model, g: GGUFFile) -> set:
             # a block never crosses a row, so the Q/K row permutation
             # applies to every plane as whole rows
             heads = {"q": cfg.num_heads, "k": cfg.num_kv_heads}.get(role)
-            if heads is not None:
+            if heads is not None and permuted:
                 planes = tuple(
                     unpermute_rope(p.reshape(p.shape[0], -1), heads)
                     .reshape(p.shape) for p in planes)
@@ -629,10 +651,13 @@ def _check_expert_metadata(cfg, g: GGUFFile) -> None:
 @torch.inference_mode()
 def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     """Load a GGUF llama checkpoint into a helix_amd Llama model
-    (dequantizing to the model dtype; Q/K rope rows un-permuted). With
+    (dequantizing to the model dtype; Q/K rope rows un-permuted, except
+    for the qwen3 / qwen3moe architectures, whose rows are not permuted in
+    the file). With
     keep_quantized, Q4_0/Q8_0 projections (WQLinear), Q4_K/Q6_K
     projections (KQLinear) and Q4_0/Q8_0 experts (MoEMLP's planes) stay
-    resident as the file's blocks; see the module docstring. A file whose
+    resident as the file's blocks; K-quant experts dequantize to bf16; see
+    the module docstring. A file whose
     expert_count / expert_used_count differ from the model's is refused."""
     g = GGUFFile(path)
     _check_expert_metadata(model.cfg, g)
@@ -644,6 +669,7 @@ def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     q, kv = cfg.q_size, cfg.kv_size
     inter = cfg.intermediate_size
     loaded = len(resident)
+    permuted = _rows_permuted(g.arch())
     for name in g.tensors:
         if name in resident:
             continue
@@ -651,9 +677,9 @@ def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
         if our not in params:
             continue
         t = g.load_tensor(name)
-        if role == "q":
+        if role == "q" and permuted:
             t = unpermute_rope(t, cfg.num_heads)
-        elif role == "k":
+        elif role == "k" and permuted:
             t = unpermute_rope(t, cfg.num_kv_heads)
         p = params[our]
         t = t.to(p.dtype)
@@ -700,19 +726,27 @@ def export_model_gguf(model, path: str, quant: str = "",
     ([E, rows, K]) and llama.expert_count / expert_used_count; q4_0 / q8_0
     quantize the experts too (quantize_ggml on the flattened rows), the
     K-quant flags leave them bf16. experts_only: quantize nothing but the
-    experts. Returns the number of tensors written."""
+    experts. A model with QK-norm (Qwen3) is written as architecture
+    qwen3 / qwen3moe: its `{arch}.*` keys, attention.key_length /
+    value_length, the attn_q_norm / attn_k_norm tensors, and Q/K rows as
+    they are (no permutation). Returns the number of tensors written."""
     if quant not in EXPORT_QUANTS:
         raise ValueError(f"quant must be one of {EXPORT_QUANTS[1:]}")
     cfg = model.cfg
 
+    moe = cfg.num_experts > 0
+    qk_norm = getattr(cfg, "qk_norm", False)
+    arch = ("qwen3moe" if moe else "qwen3") if qk_norm else "llama"
+
     def permute(w, n_head):
+        if not _rows_permuted(arch):
+            return w
         o, i = w.shape
         return (w.reshape(n_head, 2, o // n_head // 2, i)
                 .swapaxes(1, 2).reshape(o, i))
 
     sd = dict(model.named_parameters())
     q, kv, inter = cfg.q_size, cfg.kv_size, cfg.intermediate_size
-    moe = cfg.num_experts > 0
     tensors = {
         "token_embd.weight": sd["embed_tokens.weight"].data,
         "output_norm.weight": sd["final_norm_w"].data,
@@ -726,6 +760,11 @@ def export_model_gguf(model, path: str, quant: str = "",
         tensors[f"blk.{i}.attn_v.weight"] = qkv[q + kv:]
         tensors[f"blk.{i}.attn_output.weight"] = \
             sd[f"layers.{i}.attn.o_proj.weight"].data
+        if qk_norm:
+            tensors[f"blk.{i}.attn_q_norm.weight"] = \
+                sd[f"layers.{i}.attn.q_norm_w"].data
+            tensors[f"blk.{i}.attn_k_norm.weight"] = \
+                sd[f"layers.{i}.attn.k_norm_w"].data
         if moe:
             if f"layers.{i}.mlp.w13" not in sd:
                 raise ValueError("export_model_gguf: the experts of layer "
@@ -748,19 +787,27 @@ def export_model_gguf(model, path: str, quant: str = "",
         tensors[f"blk.{i}.ffn_norm.weight"] = \
             sd[f"layers.{i}.post_norm_w"].data
     meta = {
-        "general.architecture": "llama",
+        "general.architecture": arch,
         "general.name": cfg.name,
-        "llama.block_count": cfg.num_layers,
-        "llama.embedding_length": cfg.hidden_size,
-        "llama.feed_forward_length": cfg.intermediate_size,
-        "llama.attention.head_count": cfg.num_heads,
-        "llama.attention.head_count_kv": cfg.num_kv_heads,
-        "llama.context_length": cfg.max_position,
-        "llama.rope.freq_base": float(cfg.rope_base),
+        f"{arch}.block_count": cfg.num_layers,
+        f"{arch}.embedding_length": cfg.hidden_size,
+        f"{arch}.feed_forward_length": cfg.intermediate_size,
+        f"{arch}.attention.head_count": cfg.num_heads,
+        f"{arch}.attention.head_count_kv": cfg.num_kv_heads,
+        f"{arch}.context_length": cfg.max_position,
+        f"{arch}.rope.freq_base": float(cfg.rope_base),
     }
+    if qk_norm:
+        meta[f"{arch}.attention.key_length"] = cfg.head_dim
+        meta[f"{arch}.attention.value_length"] = cfg.head_dim
+        meta[f"{arch}.attention.layer_norm_rms_epsilon"] = \
+            float(cfg.rms_norm_eps)
+        if moe:
+            meta[f"{arch}.expert_feed_forward_length"] = \
+                cfg.intermediate_size
     if moe:
-        meta["llama.expert_count"] = cfg.num_experts
-        meta["llama.expert_used_count"] = cfg.experts_per_token
+        meta[f"{arch}.expert_count"] = cfg.num_experts
+        meta[f"{arch}.expert_used_count"] = cfg.experts_per_token
     if quant:
         proj = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate",
                 "ffn_up", "ffn_down")

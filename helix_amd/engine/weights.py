@@ -90,6 +90,9 @@ def _map_hf_name(name: str):
                 (f"layers.{i}.attn.qkv_proj.bias", "v"),
             "self_attn.o_proj.weight":
                 (f"layers.{i}.attn.o_proj.weight", None),
+            # Qwen3 QK-norm
+            "self_attn.q_norm.weight": (f"layers.{i}.attn.q_norm_w", None),
+            "self_attn.k_norm.weight": (f"layers.{i}.attn.k_norm_w", None),
             "mlp.gate_proj.weight":
                 (f"layers.{i}.mlp.gate_up_proj.weight", "gate"),
             "mlp.up_proj.weight":
@@ -112,6 +115,19 @@ def _map_hf_name(name: str):
                 return f"layers.{i}.mlp.w2", ("expert_down", e)
             return (f"layers.{i}.mlp.w13",
                     ("expert_gate" if parts[5] == "w1" else "expert_up", e))
+        # HF Qwen3-MoE: mlp.gate (the router) + mlp.experts.{e}.gate_proj /
+        # up_proj / down_proj, the same packing under other names
+        if rest == "mlp.gate.weight":
+            return f"layers.{i}.mlp.router_w", None
+        if len(parts) == 7 and parts[2:4] == ["mlp", "experts"] \
+                and parts[4].isdigit() and parts[6] == "weight" \
+                and parts[5] in ("gate_proj", "up_proj", "down_proj"):
+            e = int(parts[4])
+            if parts[5] == "down_proj":
+                return f"layers.{i}.mlp.w2", ("expert_down", e)
+            return (f"layers.{i}.mlp.w13",
+                    ("expert_gate" if parts[5] == "gate_proj"
+                     else "expert_up", e))
     return name, None  # our native names pass through
 
 

@@ -41,6 +41,7 @@ class LlamaConfig:
     rope_scaling: dict = field(default_factory=dict)  # llama3.1 scheme
     num_experts: int = 0           # 0 = dense MLP; > 0 = Mixtral-style MoE
     experts_per_token: int = 2
+    qk_norm: bool = False          # Qwen3: per-head RMSNorm of Q and K
 
     @property
     def q_size(self) -> int:
@@ -102,6 +103,22 @@ PRESETS = {
         intermediate_size=256, num_layers=2, num_heads=4, num_kv_heads=2,
         head_dim=64, max_position=512, rope_base=10000.0,
         num_experts=8, experts_per_token=2),
+    # Qwen3: QK-norm, no QKV bias, head_dim 128 independent of hidden_size
+    "qwen3-8b": LlamaConfig(
+        name="qwen3-8b", vocab_size=151936, hidden_size=4096,
+        intermediate_size=12288, num_layers=36, num_heads=32, num_kv_heads=8,
+        head_dim=128, rms_norm_eps=1e-6, rope_base=1000000.0,
+        max_position=40960, qk_norm=True),
+    "qwen3-32b": LlamaConfig(
+        name="qwen3-32b", vocab_size=151936, hidden_size=5120,
+        intermediate_size=25600, num_layers=64, num_heads=64, num_kv_heads=8,
+        head_dim=128, rms_norm_eps=1e-6, rope_base=1000000.0,
+        max_position=40960, qk_norm=True),
+    # q_size 512 != hidden 256, head_dim 128
+    "tiny-qwen3": LlamaConfig(
+        name="tiny-qwen3", vocab_size=512, hidden_size=256,
+        intermediate_size=512, num_layers=2, num_heads=4, num_kv_heads=2,
+        head_dim=128, max_position=512, rope_base=10000.0, qk_norm=True),
 }
 
 
@@ -172,6 +189,14 @@ class Attention(nn.Module):
         self.qkv_proj = HLinear(h, q + 2 * kv, bias=cfg.attention_bias)
         self.o_proj = HLinear(q, h, bias=False)
         self.lora = None               # LayerLoRA, set by LoRAManager
+        # Qwen3 QK-norm: one [head_dim] weight shared by all Q heads, one
+        # by all K heads; replicated under tensor parallelism
+        self.eps = cfg.rms_norm_eps
+        if cfg.qk_norm:
+            self.q_norm_w = nn.Parameter(torch.ones(self.hd))
+            self.k_norm_w = nn.Parameter(torch.ones(self.hd))
+        else:
+            self.q_norm_w = self.k_norm_w = None
 
     def forward(self, x: torch.Tensor, cos_sin: torch.Tensor, kv_cache,
                 meta) -> torch.Tensor:
@@ -185,7 +210,9 @@ class Attention(nn.Module):
         q, k, v = ops.rope_qkv_cache(
             meta.positions, qkv, cos_sin, self.nh, self.nkv, self.hd,
             kv_cache=kv_cache, slot_mapping=meta.slot_mapping,
-            want_kv=want_kv)
+            want_kv=want_kv, q_norm_w=self.q_norm_w,
+            k_norm_w=self.k_norm_w,
+            eps=self.eps if self.q_norm_w is not None else 0.0)
         if meta.is_prefill:
             if meta.cu_seqlens_k is not None:
                 # cached-prefix prefill: full-context K/V gathered from

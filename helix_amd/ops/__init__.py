@@ -91,12 +91,23 @@ def kv_fp8_dequant(t: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
 def rope_qkv_cache(positions: torch.Tensor, qkv: torch.Tensor,
                    cos_sin: torch.Tensor, num_q: int, num_kv: int,
                    head_dim: int, kv_cache=None, slot_mapping=None,
-                   want_kv: bool = False):
+                   want_kv: bool = False, q_norm_w=None, k_norm_w=None,
+                   eps: float = 0.0):
     """Fused QKV epilogue: strided split + rope + paged-cache write.
 
     Returns (q [T, num_q, head_dim], k, v) — k/v are None unless
     want_kv (fresh-prefill path needs compact K/V for attn_prefill).
+
+    q_norm_w / k_norm_w (bf16 [head_dim], both or neither) turn on Qwen3's
+    QK-norm: each Q and K head is RMS-normalised over its own head_dim
+    elements with `eps` and scaled by the weight before the rope
+    (rope_qkv_norm.hip). Without them the GPU branch issues exactly the
+    un-normed kernel.
     """
+    if (q_norm_w is None) != (k_norm_w is None):
+        raise ValueError("rope_qkv_cache: q_norm_w and k_norm_w go together "
+                         "(got only one of them)")
+    normed = q_norm_w is not None
     T = qkv.shape[0]
     if qkv.is_cuda:
         q_out = torch.empty(T, num_q * head_dim, dtype=qkv.dtype,
@@ -109,9 +120,15 @@ def rope_qkv_cache(positions: torch.Tensor, qkv: torch.Tensor,
         kc = vc = None
         if kv_cache is not None:
             kc, vc = kv_cache
-        _native().rope_qkv_cache(positions, qkv, q_out, kc, vc,
-                                 slot_mapping, k_out, v_out, cos_sin,
-                                 num_q, num_kv, head_dim)
+        if normed:
+            _native().rope_qkv_norm_cache(positions, qkv, q_out, kc, vc,
+                                          slot_mapping, k_out, v_out,
+                                          cos_sin, num_q, num_kv, head_dim,
+                                          q_norm_w, k_norm_w, eps)
+        else:
+            _native().rope_qkv_cache(positions, qkv, q_out, kc, vc,
+                                     slot_mapping, k_out, v_out, cos_sin,
+                                     num_q, num_kv, head_dim)
         return (q_out.view(T, num_q, head_dim),
                 k_out.view(T, num_kv, head_dim) if want_kv else None,
                 v_out.view(T, num_kv, head_dim) if want_kv else None)
@@ -119,7 +136,15 @@ def rope_qkv_cache(positions: torch.Tensor, qkv: torch.Tensor,
     q_sz, kv_sz = num_q * head_dim, num_kv * head_dim
     q, k, v = qkv.split([q_sz, kv_sz, kv_sz], dim=-1)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    q, k = rotary_embedding(positions, q, k, cos_sin, head_dim)
+    if normed:
+        # fp32 through norm and rope, one rounding at the end (the kernel's
+        # order); the fp8 cache below re-rounds the bf16 K on this branch
+        q = ref.qk_rms_norm(q, q_norm_w, eps, head_dim)
+        k = ref.qk_rms_norm(k, k_norm_w, eps, head_dim)
+        qr, kr = ref.rotary_embedding(positions, q, k, cos_sin, head_dim)
+        q, k = qr.to(qkv.dtype), kr.to(qkv.dtype)
+    else:
+        q, k = rotary_embedding(positions, q, k, cos_sin, head_dim)
     q = q.view(T, num_q, head_dim)
     k = k.view(T, num_kv, head_dim)
     v = v.view(T, num_kv, head_dim)

@@ -23,6 +23,17 @@ def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor,
     return rms_norm(new_res, w, eps), new_res
 
 
+def qk_rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float,
+                head_dim: int) -> torch.Tensor:
+    """Qwen3 QK-norm: RMSNorm of every head of x [T, H*head_dim] over that
+    head's head_dim elements, times w [head_dim]. Returns fp32, unrounded:
+    the rope that follows rounds once (rope_qkv_norm.hip does the same)."""
+    T = x.shape[0]
+    xf = x.float().view(T, -1, head_dim)
+    var = xf.pow(2).mean(-1, keepdim=True)
+    return (xf * torch.rsqrt(var + eps) * w.float()).view(T, -1)
+
+
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
                eps: float) -> torch.Tensor:
     return torch.nn.functional.layer_norm(

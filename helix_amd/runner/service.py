@@ -60,6 +60,11 @@ DEFAULT_SPECS = {
     # ~93 GB of bf16 weights on one MI355X; KV from what is left
     "mixtral-8x7b": ModelSpec("mixtral-8x7b", "llm", "mixtral-8x7b",
                               max_model_len=32768, kv_cache_blocks=16384),
+    "qwen3-8b": ModelSpec("qwen3-8b", "llm", "qwen3-8b",
+                          max_model_len=40960),
+    "qwen3-32b": ModelSpec("qwen3-32b", "llm", "qwen3-32b",
+                           max_model_len=40960, max_num_seqs=48,
+                           kv_cache_blocks=16384),
     "bge-base": ModelSpec("bge-base", "embedding", "bge-base"),
     "siglip-base": ModelSpec("siglip-base", "vision", "siglip-base"),
     "tiny-vit": ModelSpec("tiny-vit", "vision", "tiny-vit"),
@@ -73,6 +78,8 @@ DEFAULT_SPECS = {
                           kv_cache_blocks=256),
     "tiny-moe": ModelSpec("tiny-moe", "llm", "tiny-moe", max_model_len=256,
                           kv_cache_blocks=256),
+    "tiny-qwen3": ModelSpec("tiny-qwen3", "llm", "tiny-qwen3",
+                            max_model_len=256, kv_cache_blocks=256),
     "tiny-bert": ModelSpec("tiny-bert", "embedding", "tiny-bert"),
 }
 

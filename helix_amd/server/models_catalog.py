@@ -27,6 +27,12 @@ STATIC_MODEL_INFO: Dict[str, dict] = {
     "mixtral-8x7b": {"context_length": 32768, "prompt_price_per_m": 0.3,
                      "completion_price_per_m": 0.5, "family": "mixtral",
                      "runtime": "helix_amd", "kind": "chat"},
+    "qwen3-8b": {"context_length": 40960, "prompt_price_per_m": 0.05,
+                 "completion_price_per_m": 0.10, "family": "qwen",
+                 "runtime": "helix_amd", "kind": "chat"},
+    "qwen3-32b": {"context_length": 40960, "prompt_price_per_m": 0.3,
+                  "completion_price_per_m": 0.5, "family": "qwen",
+                  "runtime": "helix_amd", "kind": "chat"},
     "bge-base": {"context_length": 512, "prompt_price_per_m": 0.005,
                  "completion_price_per_m": 0.0, "family": "bge",
                  "runtime": "helix_amd", "kind": "embedding"},
@@ -58,6 +64,11 @@ MODEL_ALIASES: Dict[str, str] = {
     "helix-mixtral": "mixtral-8x7b",
     "mixtral:instruct": "mixtral-8x7b",
     "mistralai/Mixtral-8x7B-Instruct-v0.1": "mixtral-8x7b",
+    # the reference catalogue's current Ollama ids and their HF names
+    "qwen3:8b": "qwen3-8b",
+    "qwen3:32b": "qwen3-32b",
+    "Qwen/Qwen3-8B": "qwen3-8b",
+    "Qwen/Qwen3-32B": "qwen3-32b",
 }
 
 
