@@ -494,7 +494,13 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
                 experts_only: bool = typer.Option(
                     False, "--experts-only", help="with --quant q4_0 | "
                     "q8_0 on a mixture of experts: quantize the expert "
-                    "tensors alone")):
+                    "tensors alone"),
+                expert_quant: str = typer.Option(
+                    "", "--expert-quant", help="q4_k | q6_k | q4_k_m on a "
+                    "mixture of experts: write the expert tensors as K-quant "
+                    "super-blocks (q4_k_m: Q4_K gate/up, Q6_K down in the "
+                    "layers llama.cpp's recipe picks), whatever --quant does "
+                    "to the rest")):
     """Export a model as a GGUF v3 checkpoint (llama.cpp tensor names,
     Q/K rows permuted for GGML rope — interops with the llama.cpp
     ecosystem; see engine/gguf.py). A Qwen3 preset is written as
@@ -503,10 +509,13 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
     if quant not in ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m"):
         raise typer.BadParameter(
             "--quant must be q4_0, q8_0, q4_k, q6_k or q4_k_m")
+    if expert_quant not in ("", "q4_k", "q6_k", "q4_k_m"):
+        raise typer.BadParameter(
+            "--expert-quant must be q4_k, q6_k or q4_k_m")
     from helix_amd.engine import gguf as g
-    from helix_amd.models.llama import LlamaForCausalLM, PRESETS
+    from helix_amd.models.llama import LlamaForCausalLM, get_preset
 
-    cfg = PRESETS[preset]
+    cfg = get_preset(preset)
     model = LlamaForCausalLM(cfg)
     if ckpt:
         from helix_amd.engine.weights import load_llama_weights
@@ -515,7 +524,8 @@ def export_gguf(preset: str = typer.Option("llama3-8b"),
         model.init_random(seed)
 
     n = g.export_model_gguf(model, out, quant=quant,
-                            experts_only=experts_only)
+                            experts_only=experts_only,
+                            expert_quant=expert_quant or None)
     est = g.estimate_gguf_bytes(out)
     typer.echo(f"wrote {out}: {n} tensors, "
                f"{est['weights'] >> 20} MiB")

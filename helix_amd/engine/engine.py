@@ -21,7 +21,7 @@ from helix_amd import ops
 from helix_amd.engine.kv_cache import KVCache, chain_hash, check_block_size
 from helix_amd.engine.sampling_params import SamplingParams
 from helix_amd.models.llama import (DecodeMeta, LlamaConfig, LlamaForCausalLM,
-                                    PrefillMeta, PRESETS)
+                                    PrefillMeta, get_preset)
 
 _SEED_MIX = 0x9E3779B97F4A7C15
 
@@ -93,7 +93,7 @@ class LLMEngine:
                  tp_group=None):
         self.cfg = cfg
         self.device = torch.device(device)
-        self.model_cfg: LlamaConfig = PRESETS[cfg.model]
+        self.model_cfg: LlamaConfig = get_preset(cfg.model)
         self.tp_size = tp_size
         self.tp_rank = tp_rank
         self.tp_group = tp_group

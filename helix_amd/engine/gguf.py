@@ -25,14 +25,21 @@ re-encoding) and dequantizes them inside the GEMM:
     and up are the same one of Q4_0/Q8_0 and whose down is one of them
     become MoEMLP's quantised planes (ops/hip/moe_wq.hip). The merged
     layout is ggml's convention as documented; like the K-quant decoders it
-    has not been checked against a file written by llama.cpp.
+    has not been checked against a file written by llama.cpp;
+  * a layer's experts whose gate and up are the same one of Q4_K/Q6_K and
+    whose down is one of them become MoEMLP's K-quant planes
+    (ops/hip/moe_kq.hip), layer by layer: a Q4_K_M file's ffn_down_exps
+    are Q6_K in the layers q4_k_m_uses_q6_k selects and Q4_K in the others.
+    It needs the hidden and the expert intermediate size to be multiples
+    of 256. A layer that mixes the two families (Q4_0 gate, Q6_K down)
+    loads dense.
 Qwen3 (`general.architecture` qwen3 / qwen3moe): the per-head QK-norm
 weights `attn_q_norm` / `attn_k_norm` load as tensors, and Q/K rows are taken
 as they are: llama.cpp's converter permutes Q/K only for the llama
 architecture, Qwen uses neox (rotate-half) rope. A dense Qwen3 Q4_K_M file
 keeps its projections resident like a Llama one; a qwen3moe file keeps
-Q4_0/Q8_0 experts resident, and K-quant experts (what a Q4_K_M qwen3moe file
-holds) have no routed kernel and are dequantized to bf16. `qwen2` files are
+Q4_0/Q8_0 and Q4_K/Q6_K experts (what a Q4_K_M qwen3moe file holds)
+resident; Q5_K experts are dequantized to bf16. `qwen2` files are
 still un-permuted like llama ones (an open point, docs/PARITY.md).
 Everything else, including any other mix of types (Q4_0 with Q8_0, a
 K-quant part next to a legacy or float part) and Q5_K, is dequantized to
@@ -589,8 +596,12 @@ def _expert_tensor_names(g: GGUFFile, i: int, E: int):
 def _install_resident_experts(model, g: GGUFFile) -> set:
     """Keep a layer's experts as the file's blocks (MoEMLP's quantised
     state) when gate and up are the same one of Q4_0/Q8_0 and down is one of
-    Q4_0/Q8_0. Any other mix, K-quant experts included, is left to the
-    dense loader. Returns the GGUF tensor names consumed."""
+    Q4_0/Q8_0, or gate and up are the same one of Q4_K/Q6_K and down is one
+    of Q4_K/Q6_K (MoEMLP's K-quant state; needs H and I to be multiples of
+    256). The formats are per layer: a Q4_K_M file's ffn_down_exps are Q6_K
+    in some layers and Q4_K in the others. Any other mix, one across the two
+    families included, is left to the dense loader. Returns the GGUF tensor
+    names consumed."""
     from helix_amd import ops
     from helix_amd.models.quant import attach_wq_scratch
     cfg = model.cfg
@@ -609,7 +620,12 @@ def _install_resident_experts(model, g: GGUFFile) -> set:
         if any(len(t) != 1 for t in types):
             continue
         tg, tu, td = (next(iter(t)) for t in types)
-        if tg != tu or tg not in _WQ_FMT or td not in _WQ_FMT:
+        if tg == tu and tg in _WQ_FMT and td in _WQ_FMT:
+            family, unpack = _WQ_FMT, ops.unpack_ggml
+        elif tg == tu and tg in _KQ_FMT and td in _KQ_FMT \
+                and H % 256 == 0 and I % 256 == 0:
+            family, unpack = _KQ_FMT, ops.unpack_ggml_kq
+        else:
             continue
         shapes = [(I, H), (I, H), (H, I)]
         if any(tuple(g.tensors[n].shape) !=
@@ -619,19 +635,23 @@ def _install_resident_experts(model, g: GGUFFile) -> set:
         dev = mlp.router_w.device
         planes = []
         for part, (rows, K), t in zip(names, shapes, (tg, tu, td)):
-            fmt = _WQ_FMT[t]
-            # rows are independent: a merged tensor is [E*rows, K]
+            # rows are independent (a block or super-block never crosses a
+            # row): a merged tensor is [E*rows, K]
             n_rows = E * rows if len(part) == 1 else rows
-            got = [ops.unpack_ggml(g.read_raw(n), (n_rows, K), fmt)
+            got = [unpack(g.read_raw(n), (n_rows, K), family[t])
                    for n in part]
             planes.append(tuple(
-                torch.cat(ps, dim=0).view(E, rows, -1) for ps in zip(*got)))
+                torch.cat(ps, dim=0).view(E, rows, *ps[0].shape[1:])
+                for ps in zip(*got)))
             used.update(part)
         gate, up, down = planes
         w13 = tuple(torch.cat([a, b], dim=1).contiguous().to(dev)
                     for a, b in zip(gate, up))
         w2 = tuple(p.contiguous().to(dev) for p in down)
-        mlp.set_quantized_experts(w13, w2, (_WQ_FMT[tg], _WQ_FMT[td]))
+        if family is _KQ_FMT:
+            mlp.set_kquant_experts(w13, w2, (family[tg], family[td]))
+        else:
+            mlp.set_quantized_experts(w13, w2, (family[tg], family[td]))
     if used:
         attach_wq_scratch(model)
     return used
@@ -655,9 +675,9 @@ def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
     for the qwen3 / qwen3moe architectures, whose rows are not permuted in
     the file). With
     keep_quantized, Q4_0/Q8_0 projections (WQLinear), Q4_K/Q6_K
-    projections (KQLinear) and Q4_0/Q8_0 experts (MoEMLP's planes) stay
-    resident as the file's blocks; K-quant experts dequantize to bf16; see
-    the module docstring. A file whose
+    projections (KQLinear) and Q4_0/Q8_0 or Q4_K/Q6_K experts (MoEMLP's
+    planes) stay resident as the file's blocks; see the module docstring.
+    A file whose
     expert_count / expert_used_count differ from the model's is refused."""
     g = GGUFFile(path)
     _check_expert_metadata(model.cfg, g)
@@ -716,8 +736,12 @@ def load_gguf_weights(model, path: str, keep_quantized: bool = False) -> int:
 EXPORT_QUANTS = ("", "q4_0", "q8_0", "q4_k", "q6_k", "q4_k_m")
 
 
+EXPORT_EXPERT_QUANTS = ("q4_k", "q6_k", "q4_k_m")
+
+
 def export_model_gguf(model, path: str, quant: str = "",
-                      experts_only: bool = False) -> int:
+                      experts_only: bool = False,
+                      expert_quant: Optional[str] = None) -> int:
     """Write `model` (a dense LlamaForCausalLM, experts in bf16 if it has
     any) as a GGUF v3 checkpoint with llama.cpp tensor names, Q/K rows
     permuted for GGML rope. `quant` quantizes the projection weights (norms
@@ -726,13 +750,29 @@ def export_model_gguf(model, path: str, quant: str = "",
     ([E, rows, K]) and llama.expert_count / expert_used_count; q4_0 / q8_0
     quantize the experts too (quantize_ggml on the flattened rows), the
     K-quant flags leave them bf16. experts_only: quantize nothing but the
-    experts. A model with QK-norm (Qwen3) is written as architecture
+    experts. expert_quant ("q4_k" / "q6_k" / "q4_k_m", a mixture of experts
+    only, not next to quant q4_0 / q8_0) writes the experts as K-quant
+    super-blocks whatever `quant` does to the rest: q4_k_m is Q4_K gate and
+    up, and Q6_K down in the layers q4_k_m_uses_q6_k selects, Q4_K in the
+    others; it needs the experts' K to be a multiple of 256. A model with QK-norm (Qwen3) is written as architecture
     qwen3 / qwen3moe: its `{arch}.*` keys, attention.key_length /
     value_length, the attn_q_norm / attn_k_norm tensors, and Q/K rows as
     they are (no permutation). Returns the number of tensors written."""
     if quant not in EXPORT_QUANTS:
         raise ValueError(f"quant must be one of {EXPORT_QUANTS[1:]}")
     cfg = model.cfg
+    if expert_quant is not None:
+        if expert_quant not in EXPORT_EXPERT_QUANTS:
+            raise ValueError(
+                f"expert_quant must be one of {EXPORT_EXPERT_QUANTS}")
+        if cfg.num_experts == 0:
+            raise ValueError("expert_quant: the model has no experts")
+        if quant in ("q4_0", "q8_0"):
+            raise ValueError(f"expert_quant: quant={quant!r} already "
+                             "quantises the experts")
+        if cfg.hidden_size % 256 or cfg.intermediate_size % 256:
+            raise ValueError("expert_quant: hidden and intermediate sizes "
+                             "must be multiples of 256")
 
     moe = cfg.num_experts > 0
     qk_norm = getattr(cfg, "qk_norm", False)
@@ -840,5 +880,17 @@ def export_model_gguf(model, path: str, quant: str = "",
                                 ("token_embd.weight", "Q4_K")):
                 if tensors[name].shape[1] % 256 == 0:
                     tensors[name] = quantize_ggml(tensors[name], gtype)
+    if expert_quant is not None:
+        for name, t in list(tensors.items()):
+            part = name.split(".")[2] if name.startswith("blk.") else ""
+            if not part.endswith("_exps"):
+                continue
+            gtype = "Q6_K" if expert_quant == "q6_k" else "Q4_K"
+            if expert_quant == "q4_k_m" and part == "ffn_down_exps" and \
+                    q4_k_m_uses_q6_k(int(name.split(".")[1]), cfg.num_layers):
+                gtype = "Q6_K"
+            qt = quantize_ggml(t.reshape(-1, t.shape[2]), gtype)
+            tensors[name] = GGMLQuantized(qt.raw, tuple(t.shape),
+                                          qt.type_name)
     write_gguf(path, meta, tensors)
     return len(tensors)

@@ -121,6 +121,35 @@ PRESETS = {
         head_dim=128, max_position=512, rope_base=10000.0, qk_norm=True),
 }
 
+# Qwen3's mixtures of experts. PRESETS stays the dense families plus the
+# Mixtral pair; get_preset() resolves a name in either table, and the engine,
+# the runner and the CLI look presets up through it.
+QWEN3_MOE_PRESETS = {
+    # Qwen3-30B-A3B: Mixtral's routing at 128 experts, top-8, with Qwen3's
+    # attention; intermediate_size is per expert. The published HF config as
+    # remembered, not yet checked against a real checkpoint.
+    "qwen3-30b-a3b": LlamaConfig(
+        name="qwen3-30b-a3b", vocab_size=151936, hidden_size=2048,
+        intermediate_size=768, num_layers=48, num_heads=32, num_kv_heads=4,
+        head_dim=128, rms_norm_eps=1e-6, rope_base=1000000.0,
+        max_position=40960, qk_norm=True, num_experts=128,
+        experts_per_token=8),
+    # hidden and intermediate are multiples of 256: the experts can hold
+    # K-quant super-blocks
+    "tiny-qwen3-moe": LlamaConfig(
+        name="tiny-qwen3-moe", vocab_size=512, hidden_size=256,
+        intermediate_size=256, num_layers=2, num_heads=4, num_kv_heads=2,
+        head_dim=128, max_position=512, rope_base=10000.0, qk_norm=True,
+        num_experts=16, experts_per_token=4),
+}
+
+
+def get_preset(name: str) -> LlamaConfig:
+    """The LlamaConfig of a preset name, from PRESETS or QWEN3_MOE_PRESETS."""
+    if name in QWEN3_MOE_PRESETS:
+        return QWEN3_MOE_PRESETS[name]
+    return PRESETS[name]
+
 
 @dataclass
 class PrefillMeta:
@@ -271,6 +300,10 @@ class MLP(nn.Module):
         return out
 
 
+# plane names of a K-quant expert stack, in ops.moe_experts_kq's order
+_KQ_PLANES = {"q4_k": ("qs", "hdr"), "q6_k": ("ql", "qh", "sc", "d")}
+
+
 class MoEMLP(nn.Module):
     """Mixtral-style sparse MLP: a router over E SwiGLU experts, the top
     `experts_per_token` of them per token (ops.moe_forward). The weights are
@@ -284,7 +317,12 @@ class MoEMLP(nn.Module):
     the buffers `w13_qs`, `w13_d`, `w2_qs`, `w2_d`, with `expert_fmt` the
     (w13 format, w2 format) pair; forward runs ops.moe_forward_wq. The
     router stays a bf16 F.linear. `scratch` is the model's dequant buffer
-    for the eager library prefill path (quant.attach_wq_scratch)."""
+    for the eager library prefill path (quant.attach_wq_scratch).
+
+    K-quant state (set_kquant_experts; quant.quantize_model_experts_kq or a
+    resident load of a Q4_K_M file): the same, with ggml Q4_K/Q6_K planes in
+    the buffers `w13_<plane>` / `w2_<plane>` and forward running
+    ops.moe_forward_kq. The two families do not mix inside one layer."""
 
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -305,6 +343,12 @@ class MoEMLP(nn.Module):
         router_logits = F.linear(x, self.router_w)
         # decode runs under hipGraph capture: always the fused kernels there
         fused = True if not getattr(meta, "is_prefill", True) else None
+        if self.expert_fmt is not None and self.expert_fmt[0] in _KQ_PLANES:
+            return ops.moe_forward_kq(x, router_logits,
+                                      self.expert_planes("w13"),
+                                      self.expert_planes("w2"),
+                                      self.expert_fmt, self.k, fused=fused,
+                                      scratch=self.scratch)
         if self.expert_fmt is not None:
             return ops.moe_forward_wq(x, router_logits,
                                       (self.w13_qs, self.w13_d),
@@ -342,19 +386,68 @@ class MoEMLP(nn.Module):
             self.register_buffer(name, t.contiguous(), persistent=True)
         self.expert_fmt = (f13, f2)
 
+    def set_kquant_experts(self, w13_planes, w2_planes, fmt) -> None:
+        """Replace the bf16 experts by ggml K-quant planes ("q4_k" / "q6_k",
+        or a (w13, w2) pair; ops.moe_experts_kq has the plane shapes). Shapes
+        are checked against the config; the bf16 Parameters are deleted. The
+        planes become the buffers `w13_<plane>` / `w2_<plane>` (q4_k: qs,
+        hdr; q6_k: ql, qh, sc, d)."""
+        f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
+        e, h, i = self.num_experts, self.hidden_size, self.intermediate_size
+        if h % 256 or i % 256:
+            raise ValueError(f"MoEMLP: K-quant experts need hidden ({h}) and "
+                             f"intermediate ({i}) sizes that are multiples "
+                             f"of 256")
+        stacks = (("w13", tuple(w13_planes), f13, 2 * i, h),
+                  ("w2", tuple(w2_planes), f2, h, i))
+        for name, planes, f, rows, k in stacks:
+            ops.kq_check(f)
+            if f == "q4_k":
+                want = ((torch.uint8, (e, rows, k // 2)),
+                        (torch.uint8, (e, rows, k // 256, 16)))
+            else:
+                want = ((torch.uint8, (e, rows, k // 2)),
+                        (torch.uint8, (e, rows, k // 4)),
+                        (torch.int8, (e, rows, k // 16)),
+                        (torch.float16, (e, rows, k // 256)))
+            got = tuple((p.dtype, tuple(p.shape)) for p in planes)
+            if got != want:
+                raise ValueError(f"MoEMLP: {name} {f} planes are {got}, "
+                                 f"expected {want}")
+        for name in ("w13", "w2"):
+            if name in self._parameters:
+                del self._parameters[name]
+        for name, planes, f, _, _ in stacks:
+            for stale in [b for b in self._buffers
+                          if b.startswith(name + "_")]:
+                del self._buffers[stale]
+            for pn, t in zip(_KQ_PLANES[f], planes):
+                self.register_buffer(f"{name}_{pn}", t.contiguous(),
+                                     persistent=True)
+        self.expert_fmt = (f13, f2)
+
+    def expert_planes(self, name: str):
+        """The quantised state's planes of stack "w13" or "w2", in their
+        format's order."""
+        f = self.expert_fmt[0 if name == "w13" else 1]
+        names = _KQ_PLANES.get(f, ("qs", "d"))
+        return tuple(self._buffers[f"{name}_{pn}"] for pn in names)
+
     def _apply(self, fn, recurse=True):
-        # as WQLinear._apply: the block scales are fp16 by format and follow
-        # the device only under model.to(dtype); a scratch left on another
-        # device is dropped (attach_wq_scratch gives the model a new one)
+        # as WQLinear._apply: the fp16 scale planes (Q4_0/Q8_0 block scales,
+        # Q6_K's super-block `d`) are fp16 by format and follow the device
+        # only under model.to(dtype); a scratch left on another device is
+        # dropped (attach_wq_scratch gives the model a new one)
         if self.expert_fmt is None:
             return super()._apply(fn, recurse)
-        keep = {n: self._buffers[n] for n in ("w13_d", "w2_d")}
+        keep = {n: self._buffers[n] for n in ("w13_d", "w2_d")
+                if n in self._buffers}
         super()._apply(fn, recurse)
         for n, b in keep.items():
             if self._buffers[n].dtype != torch.float16:
                 self._buffers[n] = b.to(self._buffers[n].device)
         if self.scratch is not None \
-                and self.scratch.device != self.w13_qs.device:
+                and self.scratch.device != self.expert_planes("w13")[0].device:
             self.scratch = None
         return self
 

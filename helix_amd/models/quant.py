@@ -254,7 +254,8 @@ def _is_wq_moe(m: nn.Module) -> bool:
 
 
 def _wq_device(m: nn.Module):
-    return m.w13_qs.device if _is_wq_moe(m) else m.device
+    # the first w13 plane: `w13_qs` (Q4_0/Q8_0/Q4_K) or `w13_ql` (Q6_K)
+    return m.expert_planes("w13")[0].device if _is_wq_moe(m) else m.device
 
 
 def attach_wq_scratch(model: nn.Module) -> None:
@@ -337,6 +338,43 @@ def quantize_model_experts(model: nn.Module, fmt: str) -> int:
             planes.append((qs.view(E, rows, -1), d.view(E, rows, K // 32)))
             del w
         m.set_quantized_experts(planes[0], planes[1], fmt)
+        converted += 1
+    attach_wq_scratch(model)
+    return converted
+
+
+def quantize_model_experts_kq(model: nn.Module, fmt) -> int:
+    """quantize_model_experts for the K formats: `fmt` is "q4_k" / "q6_k", a
+    (w13, w2) pair, or "q4_k_m" (q4_k, with a q6_k w2 in the layers
+    gguf.q4_k_m_uses_q6_k picks, counting the model's MoE layers), quantised
+    by ops.quantize_kq (a plain quantizer, not ggml's search) on each
+    stack's [E*rows, K] view, layer by layer with the layer's bf16 experts
+    freed before the next. For benchmarks and tests: the engine option
+    expert_quantization does not take these formats. Returns the number of
+    layers converted; a layer already quantised is skipped."""
+    from helix_amd.engine.gguf import q4_k_m_uses_q6_k
+    from helix_amd.models.llama import MoEMLP
+    mlps = [m for m in model.modules() if isinstance(m, MoEMLP)]
+    if fmt == "q4_k_m":
+        pairs = [("q4_k", "q6_k" if q4_k_m_uses_q6_k(i, len(mlps))
+                  else "q4_k") for i in range(len(mlps))]
+    else:
+        f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
+        ops.kq_check(f13), ops.kq_check(f2)
+        pairs = [(f13, f2)] * len(mlps)
+    converted = 0
+    for m, pair in zip(mlps, pairs):
+        if m.expert_fmt is not None:
+            continue
+        stacks = []
+        for name, f in zip(("w13", "w2"), pair):
+            w = getattr(m, name).data
+            E, rows, K = w.shape
+            planes = ops.quantize_kq(w.view(E * rows, K), f)
+            stacks.append(tuple(p.view(E, rows, *p.shape[1:])
+                                for p in planes))
+            del w
+        m.set_kquant_experts(stacks[0], stacks[1], pair)
         converted += 1
     attach_wq_scratch(model)
     return converted

@@ -775,6 +775,155 @@ def moe_forward_wq(x: torch.Tensor, router_logits: torch.Tensor,
                           scratch=scratch)
 
 
+# -- routed expert GEMMs over Q4_K / Q6_K experts (ops/hip/moe_kq.hip) --
+# Largest T at which moe_experts_kq(fused=None) takes the fused kernels.
+# MOE_FUSED_MAX_T's rule: the largest benchmarked T at which the fused path
+# is not slower than this feature's own library path (a dequant_kq per
+# non-empty expert) on uniform routing, in two runs of scripts/bench_moe.py
+# --fmt q4_k / q6_k; the smaller of the two formats.
+# MEASURED, not the placeholder it started as (profiles/r11_moe_kq.md): the
+# Mixtral layer decides, and both formats give 128. Fused over library on
+# uniform routing, q4_k / q6_k, second run (first): 5.0 (4.7) / 4.0 (3.9) at
+# T = 1, 3.5 (3.3) / 2.9 (3.0) at 64, 2.4 (2.3) / 2.2 (2.2) at 128 and 0.87
+# (0.82) / 0.79 (0.79) at 512; no T between 128 and 512 was benchmarked. On
+# the Qwen3-30B-A3B layer (E = 128) the library path pays up to 256
+# dequantise launches and the fused kernels are 20-57x faster at every
+# benchmarked T, 512 included: one cutoff for all shapes leaves that on the
+# table for eager prefill above 128 tokens.
+MOE_KQ_FUSED_MAX_T = 128
+
+_MOE_KQ_NPLANES = {"q4_k": 2, "q6_k": 4}
+
+
+def moe_kq_waves(N: int, K: int, gated: bool) -> int:
+    """K-split factor (waves per workgroup) the K-quant routed GEMM uses for
+    one expert's [N, K] weight: the host's own function, a property of the
+    shape."""
+    return int(_native().moe_kq_waves(N, K, gated))
+
+
+def _moe_kq_fmt_pair(fmt):
+    f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
+    kq_check(f13), kq_check(f2)
+    return f13, f2
+
+
+def _moe_kq_planes(planes, fmt: str, what: str):
+    planes = tuple(planes)
+    if len(planes) != _MOE_KQ_NPLANES[fmt]:
+        raise ValueError(f"moe_experts_kq: {what} {fmt} takes "
+                         f"{_MOE_KQ_NPLANES[fmt]} planes, got {len(planes)}")
+    if any(p.dim() < 3 for p in planes):
+        raise ValueError(f"moe_experts_kq: {what} planes must be "
+                         f"[E, rows, ...]")
+    return planes
+
+
+def dequantize_experts_kq(planes, fmt: str,
+                          dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Expert stack planes [E, rows, ...] -> [E, rows, K] with the torch
+    reference (a super-block never crosses a row, so it is dequantize_kq on
+    E*rows rows)."""
+    E, rows = planes[0].shape[:2]
+    flat = tuple(p.reshape(E * rows, *p.shape[2:]) for p in planes)
+    return dequantize_kq(flat, fmt, dtype).view(E, rows, -1)
+
+
+def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
+                   topk_ids: torch.Tensor, topk_w: torch.Tensor,
+                   fused: bool | None = None, out: torch.Tensor | None = None,
+                   act: torch.Tensor | None = None,
+                   ypair: torch.Tensor | None = None,
+                   scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """moe_experts over experts kept as ggml Q4_K/Q6_K planes, gemm_kq's
+    planes with the expert in front: q4_k (qs [E, rows, K/2], hdr
+    [E, rows, K/256, 16]), q6_k (ql [E, rows, K/2], qh [E, rows, K/4], sc int8
+    [E, rows, K/16], d fp16 [E, rows, K/256]); rows = 2I, K = H for w13 and
+    rows = H, K = I for w2. `fmt` is "q4_k" / "q6_k" or a (w13 format, w2
+    format) pair; gate and up share a format.
+    GPU, fused=True: moe_align + the two dequant-fused routed GEMM kernels +
+    moe_combine; capture-safe, any T. GPU, fused=False: the eager library
+    path (one host sync): per non-empty expert dequant_kq of w13[e]'s plane
+    slices into `scratch`, F.linear, silu_and_mul, dequant_kq of w2[e] into
+    the same scratch (same stream, so ordered), F.linear; scaled into the
+    same fp32 ypair, the same moe_combine. `scratch` is a contiguous bf16
+    buffer of at least 2*I*H elements, allocated per call when None.
+    fused=None: fused up to MOE_KQ_FUSED_MAX_T tokens.
+    CPU: moe_experts (the torch reference) on the stacks dequantised to
+    bf16, the definition."""
+    f13, f2 = _moe_kq_fmt_pair(fmt)
+    p13 = _moe_kq_planes(w13_planes, f13, "w13")
+    p2 = _moe_kq_planes(w2_planes, f2, "w2")
+    if not x.is_cuda:
+        return ref.moe_experts(x, dequantize_experts_kq(p13, f13),
+                               dequantize_experts_kq(p2, f2),
+                               topk_ids, topk_w)
+    if x.dim() != 2 or topk_ids.dim() != 2:
+        raise ValueError("moe_experts_kq: x must be [T, H] and topk_ids "
+                         "[T, k]")
+    T, k = topk_ids.shape
+    E, I, H = p13[0].shape[0], p13[0].shape[1] // 2, p13[0].shape[2] * 2
+    P = T * k
+    if x.shape[0] != T or tuple(topk_w.shape) != (T, k):
+        raise ValueError(
+            f"moe_experts_kq: x {tuple(x.shape)}, topk_ids "
+            f"{tuple(topk_ids.shape)} and topk_w {tuple(topk_w.shape)} "
+            f"disagree on [T, k]")
+    if fused is None:
+        fused = T <= MOE_KQ_FUSED_MAX_T
+    if act is None:
+        act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
+    if ypair is None:
+        ypair = torch.empty(P, H, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(T, H, dtype=torch.bfloat16, device=x.device)
+    C = _native()
+    off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
+    pairs = torch.empty(P, dtype=torch.int32, device=x.device)
+    C.moe_align(off, pairs, topk_ids, E)
+    if fused:
+        C.moe_gemm_gated_kq(act, x, list(p13), f13, off, pairs, k)
+        C.moe_gemm_down_kq(ypair, act, list(p2), f2, topk_w, off, pairs)
+    else:
+        if x.dtype != torch.bfloat16:
+            raise ValueError("moe_experts_kq: x must be bf16 on GPU")
+        if tuple(p2[0].shape) != (E, H, I // 2) or x.shape[1] != H \
+                or tuple(act.shape) != (P, I) or tuple(ypair.shape) != (P, H) \
+                or ypair.dtype != torch.float32:
+            raise ValueError("moe_experts_kq: shape mismatch between x, the "
+                             "planes, act and ypair")
+        if scratch is None:
+            scratch = torch.empty(2 * I * H, dtype=torch.bfloat16,
+                                  device=x.device)
+        offs = off.tolist()                       # the one host sync
+        rows = pairs[:offs[E]].long()
+        xg = x[rows // k]
+        tw = topk_w.reshape(-1)[rows]
+        for e in range(E):
+            lo, hi = offs[e], offs[e + 1]
+            if hi == lo:
+                continue
+            w = dequant_kq([p[e] for p in p13], f13, out=scratch)
+            a = silu_and_mul(torch.nn.functional.linear(xg[lo:hi], w))
+            act[rows[lo:hi]] = a
+            w = dequant_kq([p[e] for p in p2], f2, out=scratch)
+            y = torch.nn.functional.linear(a, w)
+            ypair[rows[lo:hi]] = y.float() * tw[lo:hi, None]
+    C.moe_combine(out, ypair, k)
+    return out
+
+
+def moe_forward_kq(x: torch.Tensor, router_logits: torch.Tensor,
+                   w13_planes, w2_planes, fmt, k: int,
+                   fused: bool | None = None,
+                   scratch: torch.Tensor | None = None) -> torch.Tensor:
+    """One MoE MLP over K-quant experts: route (moe_route) and run the
+    routed experts (moe_experts_kq)."""
+    ids, w = moe_route(router_logits, k)
+    return moe_experts_kq(x, w13_planes, w2_planes, fmt, ids, w, fused=fused,
+                          scratch=scratch)
+
+
 def mfma_probe(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     d = torch.empty(16, 16, dtype=torch.float32, device=a.device)
     _native().mfma_probe(d, a, b)

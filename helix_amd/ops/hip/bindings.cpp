@@ -102,6 +102,15 @@ void moe_gemm_down_wq(torch::Tensor ypair, torch::Tensor act,
                       torch::Tensor topk_w, torch::Tensor expert_off,
                       torch::Tensor sorted_pairs);
 int64_t moe_waves(int64_t N, int64_t K, bool gated);
+void moe_gemm_gated_kq(torch::Tensor act, torch::Tensor x,
+                       std::vector<torch::Tensor> w13_planes, std::string fmt,
+                       torch::Tensor expert_off, torch::Tensor sorted_pairs,
+                       int64_t k);
+void moe_gemm_down_kq(torch::Tensor ypair, torch::Tensor act,
+                      std::vector<torch::Tensor> w2_planes, std::string fmt,
+                      torch::Tensor topk_w, torch::Tensor expert_off,
+                      torch::Tensor sorted_pairs);
+int64_t moe_kq_waves(int64_t N, int64_t K, bool gated);
 int64_t moe_max_experts();
 int64_t moe_max_topk();
 int64_t moe_chunk_pairs();
@@ -180,6 +189,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_waves", &moe_waves,
         "K-split factor (waves per workgroup) moe_gemm uses for one expert's "
         "[N, K] weight");
+  m.def("moe_gemm_gated_kq", &moe_gemm_gated_kq,
+        "Routed expert GEMM 1 over Q4_K/Q6_K expert planes, dequant fused "
+        "into the MFMA loop");
+  m.def("moe_gemm_down_kq", &moe_gemm_down_kq,
+        "Routed expert GEMM 2 over Q4_K/Q6_K expert planes, fp32 ypair");
+  m.def("moe_kq_waves", &moe_kq_waves,
+        "K-split factor (waves per workgroup) moe_gemm_*_kq uses for one "
+        "expert's [N, K] weight");
   m.attr("MOE_MAX_EXPERTS") = moe_max_experts();
   m.attr("MOE_MAX_TOPK") = moe_max_topk();
   m.attr("MOE_CHUNK_PAIRS") = moe_chunk_pairs();

@@ -1,5 +1,6 @@
 // Register-level dequantization helpers shared by the weight-only GEMMs
-// (gemm_wq.hip and moe_wq.hip: ggml Q4_0/Q8_0, gemm_kq.hip: ggml Q4_K/Q6_K).
+// (gemm_wq.hip and moe_wq.hip: ggml Q4_0/Q8_0; gemm_kq.hip and moe_kq.hip:
+// ggml Q4_K/Q6_K, through kq_common.h).
 #pragma once
 
 #include "common.h"

@@ -1,5 +1,6 @@
 // Limits and host-side checks shared by the routed expert GEMMs
-// (moe.hip: bf16 experts, moe_wq.hip: ggml Q4_0/Q8_0 experts).
+// (moe.hip: bf16 experts, moe_wq.hip: ggml Q4_0/Q8_0 experts, moe_kq.hip:
+// ggml Q4_K/Q6_K experts).
 #pragma once
 
 #include "common.h"

@@ -22,7 +22,7 @@ import torch
 from helix_amd.engine.engine import EngineConfig, LLMEngine, Sequence
 from helix_amd.engine.sampling_params import SamplingParams
 from helix_amd.models.bert import BERT_PRESETS, BertEmbeddingModel
-from helix_amd.models.llama import PRESETS as LLAMA_PRESETS
+from helix_amd.models.llama import PRESETS as LLAMA_PRESETS, get_preset
 from helix_amd.utils.tokenizer import get_tokenizer
 
 log = logging.getLogger("helix_amd.runner")
@@ -65,6 +65,10 @@ DEFAULT_SPECS = {
     "qwen3-32b": ModelSpec("qwen3-32b", "llm", "qwen3-32b",
                            max_model_len=40960, max_num_seqs=48,
                            kv_cache_blocks=16384),
+    # ~61 GB of bf16 weights (58 GB of them experts); bf16 experts by
+    # default like mixtral-8x7b, a Q4_K_M file loaded resident is ~17 GB
+    "qwen3-30b-a3b": ModelSpec("qwen3-30b-a3b", "llm", "qwen3-30b-a3b",
+                               max_model_len=40960, kv_cache_blocks=16384),
     "bge-base": ModelSpec("bge-base", "embedding", "bge-base"),
     "siglip-base": ModelSpec("siglip-base", "vision", "siglip-base"),
     "tiny-vit": ModelSpec("tiny-vit", "vision", "tiny-vit"),
@@ -80,6 +84,8 @@ DEFAULT_SPECS = {
                           kv_cache_blocks=256),
     "tiny-qwen3": ModelSpec("tiny-qwen3", "llm", "tiny-qwen3",
                             max_model_len=256, kv_cache_blocks=256),
+    "tiny-qwen3-moe": ModelSpec("tiny-qwen3-moe", "llm", "tiny-qwen3-moe",
+                                max_model_len=256, kv_cache_blocks=256),
     "tiny-bert": ModelSpec("tiny-bert", "embedding", "tiny-bert"),
 }
 
@@ -110,7 +116,7 @@ def estimate_model_bytes(spec: ModelSpec, block_size: int = 16) -> int:
         per_layer = 4 * cfg.hidden_size ** 2 + \
             2 * cfg.hidden_size * cfg.intermediate_size
         return 2 * (n + cfg.num_layers * per_layer) + (64 << 20)
-    cfg = LLAMA_PRESETS[spec.preset]
+    cfg = get_preset(spec.preset)
     emb = cfg.vocab_size * cfg.hidden_size * (1 if cfg.tie_embeddings else 2)
     mlp = 3 * cfg.hidden_size * cfg.intermediate_size
     experts = 0                     # expert weights held as ggml blocks
@@ -163,7 +169,7 @@ class LLMInstance:
         if kv_blocks is None and torch.cuda.is_available():
             free, total = torch.cuda.mem_get_info(torch.device(device))
             from helix_amd.engine.kv_cache import KVCache
-            cfg = LLAMA_PRESETS[spec.preset]
+            cfg = get_preset(spec.preset)
             budget = int(total * spec.kv_memory_fraction)
             kv_blocks = KVCache.blocks_for_bytes(
                 min(budget, max(free - (2 << 30), 1 << 28)),

@@ -68,7 +68,7 @@ def _tp_worker(rank: int, world: int, preset: str, engine_kwargs: dict,
     import torch.distributed as dist
     from helix_amd import parallel
     from helix_amd.engine.engine import EngineConfig, LLMEngine
-    from helix_amd.models.llama import LlamaForCausalLM, PRESETS
+    from helix_amd.models.llama import LlamaForCausalLM, get_preset
 
     try:
         if device_type == "cuda":
@@ -78,7 +78,7 @@ def _tp_worker(rank: int, world: int, preset: str, engine_kwargs: dict,
         else:
             device = "cpu"
         parallel.init_tp(world, backend=backend)
-        cfg = PRESETS[preset]
+        cfg = get_preset(preset)
         # One-shot xGMI allreduce sized for the decode messages
         # (B x hidden bf16); prefill messages exceed it and fall back to
         # RCCL rings automatically (both correct, SURVEY §2.6 plan).

@@ -33,6 +33,11 @@ STATIC_MODEL_INFO: Dict[str, dict] = {
     "qwen3-32b": {"context_length": 40960, "prompt_price_per_m": 0.3,
                   "completion_price_per_m": 0.5, "family": "qwen",
                   "runtime": "helix_amd", "kind": "chat"},
+    # the reference lists a 256K context for qwen3:30b; served at the other
+    # Qwen3 presets' 40960 (no long-rope variant)
+    "qwen3-30b-a3b": {"context_length": 40960, "prompt_price_per_m": 0.1,
+                      "completion_price_per_m": 0.3, "family": "qwen",
+                      "runtime": "helix_amd", "kind": "chat"},
     "bge-base": {"context_length": 512, "prompt_price_per_m": 0.005,
                  "completion_price_per_m": 0.0, "family": "bge",
                  "runtime": "helix_amd", "kind": "embedding"},
@@ -69,6 +74,8 @@ MODEL_ALIASES: Dict[str, str] = {
     "qwen3:32b": "qwen3-32b",
     "Qwen/Qwen3-8B": "qwen3-8b",
     "Qwen/Qwen3-32B": "qwen3-32b",
+    "qwen3:30b": "qwen3-30b-a3b",
+    "Qwen/Qwen3-30B-A3B": "qwen3-30b-a3b",
 }
 
 

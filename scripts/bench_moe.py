@@ -25,6 +25,11 @@ dequantise per non-empty expert. weight_bytes then counts the blocks
 (18 / 34 bytes per 32 weights). Run bf16 and the quantised formats in one
 session to compare them.
 
+--fmt q4_k | q6_k times ops.moe_forward_kq on the layer held as ggml
+Q4_K / Q6_K super-block planes (random payload and scale codes, small finite
+fp16 d / dmin); H and I must be multiples of 256. weight_bytes counts the
+super-blocks (144 / 210 bytes per 256 weights).
+
 A GPU is required; there is no CPU fallback. Run under a time limit, e.g.
     timeout 600 python scripts/bench_moe.py --out moe.jsonl
 """
@@ -54,7 +59,7 @@ def main():
     ap.add_argument("--t", type=int, action="append")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--fmt", default="bf16", choices=("bf16", "q4_0", "q8_0"))
+    ap.add_argument("--fmt", default="bf16", choices=("bf16", "q4_0", "q8_0", "q4_k", "q6_k"))
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -63,8 +68,13 @@ def main():
     dev = torch.device("cuda:0")
     E, k, H, I = args.experts, args.topk, args.hidden, args.inter
     fmt = args.fmt
-    blk_bytes = {"bf16": 64, "q4_0": 18, "q8_0": 34}[fmt]   # per 32 weights
-    expert_bytes = 3 * H * I * blk_bytes // 32
+    kq = fmt in ("q4_k", "q6_k")
+    if kq and (H % 256 or I % 256):
+        sys.exit(f"--fmt {fmt} needs --hidden and --inter to be multiples "
+                 f"of 256")
+    blk_bytes = {"bf16": 512, "q4_0": 144, "q8_0": 272, "q4_k": 144,
+                 "q6_k": 210}[fmt]                          # per 256 weights
+    expert_bytes = 3 * H * I * blk_bytes // 256
     # the least a call activates is k experts; keep two uses of a weight
     # more than the last-level cache apart
     copies = max(2, -(-CACHE_BYTES // (k * expert_bytes)))
@@ -81,7 +91,30 @@ def main():
         d.uniform_(0.5, 1.5, generator=g)
         return qs, (d * (std / qstd)).to(torch.float16)
 
+    def rbytes(*shape):
+        return torch.randint(0, 256, shape, dtype=torch.uint8, device=dev,
+                             generator=g)
+
+    def kq_planes(rows, K, std):
+        d = torch.empty(E, rows, K // 256, device=dev)
+        d.uniform_(0.5, 1.5, generator=g)
+        if fmt == "q4_k":
+            # (d*sc)*nib - dmin*m with 6-bit sc, m: keep the std near `std`
+            hdr = rbytes(E, rows, K // 256, 16)
+            hdr[..., 0:2] = (d * (std / 150)).to(torch.float16)[..., None] \
+                .view(torch.uint8)
+            hdr[..., 2:4] = (d * (std / 30)).to(torch.float16)[..., None] \
+                .view(torch.uint8)
+            return rbytes(E, rows, K // 2), hdr
+        return (rbytes(E, rows, K // 2), rbytes(E, rows, K // 4),
+                rbytes(E, rows, K // 16).view(torch.int8),
+                (d * (std / 1400)).to(torch.float16))
+
     for _ in range(copies):
+        if kq:
+            layers.append((kq_planes(2 * I, H, H ** -0.5),
+                           kq_planes(H, I, I ** -0.5)))
+            continue
         if fmt != "bf16":
             layers.append((planes(2 * I, H, H ** -0.5),
                            planes(H, I, I ** -0.5)))
@@ -94,6 +127,9 @@ def main():
 
     def call(fused, x, logits, i):
         w13, w2 = layers[i % copies]
+        if kq:
+            return ops.moe_forward_kq(x, logits, w13, w2, fmt, k, fused=fused,
+                                      scratch=scratch)
         if fmt != "bf16":
             return ops.moe_forward_wq(x, logits, w13, w2, fmt, k, fused=fused,
                                       scratch=scratch)

@@ -3,7 +3,10 @@
 configuration: --model, --batch (= max_num_seqs, all slots busy) and
 --quant in {none, q8_0, q4_0}; a mixture-of-experts preset takes
 --expert-quant in {none, q8_0, q4_0} instead (its experts alone are
-quantised). Prints one JSON line.
+quantised), or q4_k / q6_k / q4_k_m: the model is then built in bf16 on the
+GPU, its experts are quantised layer by layer
+(quant.quantize_model_experts_kq) and it is handed to the engine as it is.
+Prints one JSON line.
 
 One configuration per process, so every run starts from a cold allocator
 and can carry its own time limit:
@@ -34,7 +37,8 @@ def main():
     ap.add_argument("--quant", default="none",
                     choices=["none", "q8_0", "q4_0"])
     ap.add_argument("--expert-quant", default="none",
-                    choices=["none", "q8_0", "q4_0"])
+                    choices=["none", "q8_0", "q4_0", "q4_k", "q6_k",
+                             "q4_k_m"])
     ap.add_argument("--prompt-len", type=int, default=32)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
@@ -46,9 +50,17 @@ def main():
         model=args.model, max_num_seqs=args.batch, max_model_len=max_len,
         kv_cache_blocks=args.batch * (max_len // 16 + 2), eos_token_id=-1,
         quantization=None if args.quant == "none" else args.quant,
-        expert_quantization=None if args.expert_quant == "none"
-        else args.expert_quant)
-    eng = LLMEngine(cfg, device="cuda:0")
+        expert_quantization=args.expert_quant
+        if args.expert_quant in ("q8_0", "q4_0") else None)
+    model = None
+    if args.expert_quant in ("q4_k", "q6_k", "q4_k_m"):
+        from helix_amd.models.llama import LlamaForCausalLM, get_preset
+        from helix_amd.models.quant import quantize_model_experts_kq
+        model = LlamaForCausalLM(get_preset(args.model)).to(torch.bfloat16) \
+            .to("cuda:0")
+        model.init_random(cfg.seed)
+        quantize_model_experts_kq(model, args.expert_quant)
+    eng = LLMEngine(cfg, device="cuda:0", model=model)
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     model_bytes = sum(t.numel() * t.element_size() for t in
