@@ -74,14 +74,17 @@ def quantize_model_fp8(model: nn.Module,
 class WQLinear(nn.Module):
     """Drop-in nn.Linear replacement holding ggml Q4_0/Q8_0 planes:
     `qs` (payload bytes) and `d` (fp16 block scales), plus an optional
-    bias. Up to ops.WQ_FUSED_MAX_M rows run the fused dequant GEMM; larger
-    batches dequantize into `scratch` and use the library GEMM.
+    bias. Up to ops.WQ_FUSED_MAX_M rows run the fused dequant GEMM, up to
+    ops.WQ_TILED_MAX_M rows the LDS-tiled split-K kernel, which keeps its
+    fp32 partial sums in `scratch`; larger batches dequantize into
+    `scratch` and use the library GEMM.
 
     `scratch` is a bf16 buffer owned by the MODEL this module belongs to
     (attach_wq_scratch): its layers run one after another on one stream
-    and may share it, two models may not, because the large-M path is two
-    launches (dequantize, GEMM) that another model's thread can get
-    between. Without one the large-M path allocates per call."""
+    and may share it, two models may not, because both paths that use it
+    are two launches (split-K GEMM and reduction, or dequantize and GEMM)
+    that another model's thread can get between. Without one those paths
+    allocate per call."""
 
     def __init__(self, qs: torch.Tensor, d: torch.Tensor, fmt: str,
                  bias: torch.Tensor | None = None,

@@ -375,6 +375,15 @@ from .reference import (quantize_wq, dequantize_wq, pack_ggml,  # noqa: E402,F40
 # (profiles/r05_wq.md: 0.99-2.4x at M = 16, 0.81-1.8x at M = 32).
 WQ_FUSED_MAX_M = 16
 
+# Largest M the LDS-tiled split-K kernel (gemm_wq_tiled.hip) serves; above
+# it dequant_wq + the library GEMM. The same rule: the largest member of
+# graph_runner.BATCH_BUCKETS at which the kernel is not slower than that
+# fallback for both formats at all four llama3-8b projection shapes, in two
+# runs (profiles/r12_wq_tiled.md: 0.62-0.72x of the fallback's time at
+# M = 128; at 192 gate_up_proj q8_0 loses, 140 against 133-137 us). The
+# kernel itself is correct for any M.
+WQ_TILED_MAX_M = 128
+
 
 def dequant_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
                out: torch.Tensor | None = None) -> torch.Tensor:
@@ -399,15 +408,25 @@ def dequant_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
     return w
 
 
+def wq_tiled_splits(N: int, K: int) -> int:
+    """K-split factor (grid.z) the tiled kernel uses for a [N, K] weight:
+    the host's own function, a property of the shape."""
+    return int(_native().wq_tiled_splits(N, K))
+
+
 def gemm_wq(x: torch.Tensor, qs: torch.Tensor, d: torch.Tensor, fmt: str,
             bias: torch.Tensor | None = None,
             scratch: torch.Tensor | None = None) -> torch.Tensor:
     """out[M,N] = x[M,K] @ dequant(qs, d)^T (+ bias): ggml Q4_0/Q8_0
     weights kept quantized. GPU, M <= WQ_FUSED_MAX_M: dequant fused into the
-    MFMA loop. GPU, larger M: dequant_wq into `scratch` (allocated per call
-    when None, so capture-safe callers pass one) + the library GEMM.
-    CPU: F.linear on the dequantized weight, the definition tests hold the
-    rest of the stack to."""
+    MFMA loop (gemm_wq.hip). GPU, M <= WQ_TILED_MAX_M: the LDS-tiled split-K
+    kernel (gemm_wq_tiled.hip); a weight it splits KS = wq_tiled_splits(N, K)
+    > 1 ways needs KS*M*N fp32 partial sums, which live in `scratch` viewed
+    as fp32, and a `scratch` too small for them sends the call down the
+    next path. GPU, larger M: dequant_wq into `scratch` + the library GEMM.
+    `scratch` is allocated per call when None, so capture-safe callers pass
+    one. CPU: F.linear on the dequantized weight, the definition tests hold
+    the rest of the stack to."""
     bits = wq_bits(fmt)
     if not x.is_cuda:
         w = dequantize_wq(qs, d, fmt, torch.float32).to(x.dtype)
@@ -421,8 +440,30 @@ def gemm_wq(x: torch.Tensor, qs: torch.Tensor, d: torch.Tensor, fmt: str,
         return out
     if x.dtype != torch.bfloat16:
         raise ValueError(f"gemm_wq: x must be bf16 on GPU, got {x.dtype}")
+    if 0 < M <= WQ_TILED_MAX_M:
+        ws = _wq_tiled_ws(M, N, x.shape[1], scratch, x.device)
+        if ws is not False:
+            out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+            _native().gemm_wq_tiled(out, x, qs, d, bias, bits, ws)
+            return out
     w = dequant_wq(qs, d, fmt, out=scratch)
     return torch.nn.functional.linear(x, w, bias)
+
+
+def _wq_tiled_ws(M: int, N: int, K: int, scratch: torch.Tensor | None,
+                 device):
+    """The tiled kernel's fp32 workspace for a [N, K] weight at M rows:
+    None when it needs none, a view of `scratch` (a new buffer without
+    one), or False when `scratch` cannot hold it."""
+    need = wq_tiled_splits(N, K) * M * N
+    if need == M * N:
+        return None
+    if scratch is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    if scratch.dtype != torch.bfloat16 or not scratch.is_contiguous() \
+            or scratch.numel() < 2 * need or scratch.data_ptr() % 16:
+        return False
+    return scratch.view(-1)[:2 * need].view(torch.float32)
 
 
 # -- ggml Q4_K / Q6_K weight-only GEMM (ops/hip/gemm_kq.hip) ------------

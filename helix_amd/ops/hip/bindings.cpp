@@ -75,6 +75,10 @@ void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
 void dequant_wq(torch::Tensor out, torch::Tensor qs, torch::Tensor d,
                 int64_t bits);
 int64_t wq_kernel_max_m();
+void gemm_wq_tiled(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
+                   torch::Tensor d, c10::optional<torch::Tensor> bias,
+                   int64_t bits, c10::optional<torch::Tensor> ws);
+int64_t wq_tiled_splits(int64_t N, int64_t K);
 void gemm_kq(torch::Tensor out, int64_t col_off, torch::Tensor x,
              std::vector<torch::Tensor> planes,
              c10::optional<torch::Tensor> bias, std::string fmt);
@@ -161,6 +165,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dequant_wq", &dequant_wq,
         "Q4_0/Q8_0 planes -> bf16 [N,K] into a caller buffer");
   m.attr("WQ_KERNEL_MAX_M") = wq_kernel_max_m();
+  m.def("gemm_wq_tiled", &gemm_wq_tiled,
+        "Q4_0/Q8_0 weight-only GEMM for any M: x tile in LDS, split K "
+        "(fp32 workspace ws when wq_tiled_splits > 1)");
+  m.def("wq_tiled_splits", &wq_tiled_splits,
+        "K-split factor (grid.z) gemm_wq_tiled uses for a [N,K] weight");
   m.def("gemm_kq", &gemm_kq,
         "Q4_K/Q6_K weight-only GEMM into out[:, col_off:col_off+N], dequant "
         "fused into the MFMA loop (M <= 32)");

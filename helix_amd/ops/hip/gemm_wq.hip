@@ -207,9 +207,13 @@ __global__ __launch_bounds__(256) void dequant_wq_kernel(
       __builtin_bit_cast(u32x4, r);
 }
 
+}  // namespace
+
 // Shape / dtype / layout contract of a (qs, d) pair. Returns N; sets K.
-int64_t check_planes(const torch::Tensor& qs, const torch::Tensor& d,
-                     int64_t bits, int64_t* K_out) {
+// Shared with gemm_wq_tiled.hip.
+namespace helix {
+int64_t wq_check_planes(const torch::Tensor& qs, const torch::Tensor& d,
+                        int64_t bits, int64_t* K_out) {
   TORCH_CHECK(bits == 4 || bits == 8, "gemm_wq: bits must be 4 or 8");
   TORCH_CHECK(qs.is_cuda() && d.is_cuda(), "gemm_wq: planes must be on GPU");
   TORCH_CHECK(qs.dim() == 2 && d.dim() == 2, "gemm_wq: planes must be 2-D");
@@ -238,6 +242,9 @@ int64_t check_planes(const torch::Tensor& qs, const torch::Tensor& d,
   *K_out = K;
   return N;
 }
+}  // namespace helix
+
+namespace {
 
 template <int BITS, int MT, int CT, int W>
 void launch_one(torch::Tensor& out, const torch::Tensor& x,
@@ -298,7 +305,7 @@ void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
              torch::Tensor d, c10::optional<torch::Tensor> bias,
              int64_t bits) {
   int64_t K64 = 0;
-  const int64_t N = check_planes(qs, d, bits, &K64);
+  const int64_t N = wq_check_planes(qs, d, bits, &K64);
   TORCH_CHECK(x.is_cuda() && out.is_cuda(), "gemm_wq: x/out must be on GPU");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
               out.scalar_type() == torch::kBFloat16,
@@ -344,7 +351,7 @@ void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
 void dequant_wq(torch::Tensor out, torch::Tensor qs, torch::Tensor d,
                 int64_t bits) {
   int64_t K = 0;
-  const int64_t N = check_planes(qs, d, bits, &K);
+  const int64_t N = wq_check_planes(qs, d, bits, &K);
   TORCH_CHECK(out.is_cuda() && out.device() == qs.device() &&
               out.scalar_type() == torch::kBFloat16 && out.dim() == 2 &&
               out.size(0) == N && out.size(1) == K && out.is_contiguous(),

@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import helix_amd.ops as ops  # noqa: E402
 
 SHAPES = ["6144x4096", "4096x4096", "28672x4096", "4096x14336"]   # N x K
-MS = [1, 4, 16, 64, 128, 512]
+MS = [1, 4, 16, 32, 64, 128, 256, 512]
 CACHE_BYTES = 768 << 20       # rotate over at least this many weight bytes
 
 
@@ -47,9 +47,14 @@ def weight_bytes(variant: str, N: int, K: int) -> int:
     return N * K * BYTES_PER_256[variant] // 256
 
 
-def fused_max_m(variant: str) -> int:
-    return ops.KQ_FUSED_MAX_M if variant in ops.KQ_FORMATS \
-        else ops.WQ_FUSED_MAX_M
+def path(variant: str, M: int) -> str:
+    if variant == "bf16":
+        return "library"
+    if variant in ops.KQ_FORMATS:
+        return "fused" if M <= ops.KQ_FUSED_MAX_M else "dequant+library"
+    if M <= ops.WQ_FUSED_MAX_M:
+        return "fused"
+    return "tiled" if M <= ops.WQ_TILED_MAX_M else "dequant+library"
 
 
 def main():
@@ -64,6 +69,10 @@ def main():
                     help="time the fused kernels up to this M instead of "
                     "the shipped cutoffs (to measure where the cutoff "
                     "belongs)")
+    ap.add_argument("--tiled-max-m", type=int, default=-1,
+                    help="time the tiled Q4_0/Q8_0 kernel up to this M "
+                    "instead of the shipped cutoff; 0 forces dequant + "
+                    "library above the fused cutoff")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -74,6 +83,8 @@ def main():
     if args.fused_max_m:
         ops.WQ_FUSED_MAX_M = min(args.fused_max_m, ops._C.WQ_KERNEL_MAX_M)
         ops.KQ_FUSED_MAX_M = min(args.fused_max_m, ops._C.KQ_KERNEL_MAX_M)
+    if args.tiled_max_m >= 0:
+        ops.WQ_TILED_MAX_M = args.tiled_max_m
     dev = torch.device("cuda:0")
     lines = []
     for shape in args.shape or SHAPES:
@@ -124,9 +135,7 @@ def main():
             for v, ts in times.items():
                 med, mn = statistics.median(ts), min(ts)
                 rec = {"N": N, "K": K, "M": M, "variant": v,
-                       "path": ("library" if v == "bf16" else
-                                "fused" if M <= fused_max_m(v)
-                                else "dequant+library"),
+                       "path": path(v, M),
                        "us_median": round(med, 2), "us_min": round(mn, 2),
                        "weight_bytes": weight_bytes(v, N, K),
                        "weight_GBps": round(
