@@ -154,10 +154,16 @@ class KQLinear(nn.Module):
     format, `rows[i]` its first output row.
 
     Up to ops.KQ_FUSED_MAX_M rows: one fused dequant GEMM launch per
-    segment, each writing its columns of one [M, N] output. Larger batches:
-    every segment dequantizes into its row range of `scratch`, then one
-    library GEMM over the whole weight. `scratch` follows WQLinear's
-    ownership rule (attach_wq_scratch): one buffer per model and GPU."""
+    segment, each writing its columns of one [M, N] output. Up to
+    ops.KQ_TILED_MAX_M rows, when every segment has N % 64 == 0: one launch
+    of the LDS-tiled split-K kernel per segment into the same kind of
+    output; the segments run in order on one stream and share one fp32
+    workspace for their partial sums, `scratch` viewed as fp32. Otherwise
+    (larger batches, a narrower segment, a scratch too small for the
+    partial sums) every segment dequantizes into its row range of
+    `scratch`, then one library GEMM over the whole weight. `scratch`
+    follows WQLinear's ownership rule (attach_wq_scratch): one buffer per
+    model and GPU."""
 
     def __init__(self, segments, bias: torch.Tensor | None = None,
                  scratch: torch.Tensor | None = None):
@@ -240,11 +246,23 @@ class KQLinear(nn.Module):
                 ops.gemm_kq(x2, self.planes(i), fmt, self.bias, out=out,
                             col_off=self.rows[i])
             return out.reshape(*shape, N)
+        ends = self.rows[1:] + [N]
+        if 0 < M <= ops.KQ_TILED_MAX_M and x2.dtype == torch.bfloat16 \
+                and all((e - r) % 64 == 0 for r, e in zip(self.rows, ends)):
+            ws = ops._kq_tiled_ws(
+                M, [(e - r, K) for r, e in zip(self.rows, ends)],
+                self.scratch, x2.device)
+            if ws is not False:
+                out = torch.empty(M, N, dtype=x2.dtype, device=x2.device)
+                for i, fmt in enumerate(self.fmts):
+                    ops._native().gemm_kq_tiled(
+                        out, self.rows[i], x2, list(self.planes(i)),
+                        self.bias, fmt, ws)
+                return out.reshape(*shape, N)
         if self.scratch is not None:
             w = self.scratch.view(-1)[:N * K].view(N, K)
         else:
             w = torch.empty(N, K, dtype=torch.bfloat16, device=x2.device)
-        ends = self.rows[1:] + [N]
         for i, fmt in enumerate(self.fmts):
             ops.dequant_kq(self.planes(i), fmt, out=w[self.rows[i]:ends[i]])
         out = torch.nn.functional.linear(x2, w, self.bias)

@@ -480,6 +480,24 @@ from .reference import (quantize_kq, dequantize_kq, pack_ggml_kq,  # noqa: E402,
 # losing).
 KQ_FUSED_MAX_M = 16
 
+# Largest M the LDS-tiled split-K K-quant kernel (gemm_kq_tiled.hip) serves;
+# above it dequant_kq + the library GEMM. WQ_TILED_MAX_M's rule: the largest
+# member of graph_runner.BATCH_BUCKETS at which the kernel is not slower than
+# that fallback for both formats at all four llama3-8b projection shapes, in
+# two runs. MEASURED (profiles/r13_kq_tiled.md), tiled / fallback time,
+# min-max over shapes, formats and runs: 0.28-0.53 at M = 32, 0.36-0.53 at
+# 64, 0.45-0.68 at 128, 0.55-0.85 at 192; at 256 gate_up_proj q6_k loses in
+# both runs (141.0 against 135.3 us, 140.4 against 137.8). The speed rule
+# alone gives 192. Shipped: 128, the sibling's value. At 192 the 160-token
+# prefill of tests/test_kq_gpu.py::test_q4_k_engine_fallback_path_gpu moves
+# from the library GEMM (the bf16 reference engine's own arithmetic) to this
+# kernel, and one of its 32 greedy tiny-gqa sequences then matches the
+# reference on 4 of its first 12 tokens against the bar of 6. Whether that
+# is a near-tie flipped by accumulation order alone was not established, so
+# the bucket 192 is left to a follow-up. The kernel itself is correct for
+# any M.
+KQ_TILED_MAX_M = 128
+
 
 def kq_waves(N: int, K: int) -> int:
     """K-split factor (waves per workgroup) the fused kernel uses for a
@@ -519,10 +537,14 @@ def gemm_kq(x: torch.Tensor, planes, fmt: str,
     `out` is a bf16 [M, ldo] buffer shared by the segments of a fused
     projection (allocated [M, N] when None, with col_off = 0); `bias`
     is indexed like `out`'s columns. Returns `out`.
-    GPU, M <= KQ_FUSED_MAX_M: dequant fused into the MFMA loop. GPU, larger
-    M: dequant_kq into `scratch` (allocated per call when None) + the
-    library GEMM. CPU: F.linear on the dequantized weight, the definition
-    tests hold the rest of the stack to."""
+    GPU, M <= KQ_FUSED_MAX_M: dequant fused into the MFMA loop. GPU,
+    M <= KQ_TILED_MAX_M and N % 64 == 0: the LDS-tiled split-K kernel
+    (gemm_kq_tiled.hip); a weight it splits KS = kq_tiled_splits(N, K) > 1
+    ways keeps KS*M*N fp32 partial sums in `scratch` viewed as fp32, and a
+    `scratch` too small for them sends the call down the next path. GPU,
+    otherwise: dequant_kq into `scratch` + the library GEMM. `scratch` is
+    allocated per call when None. CPU: F.linear on the dequantized weight,
+    the definition tests hold the rest of the stack to."""
     kq_check(fmt)
     N, K = kq_shape(planes, fmt)
     if x.dim() != 2:
@@ -545,12 +567,48 @@ def gemm_kq(x: torch.Tensor, planes, fmt: str,
     elif x.dtype != torch.bfloat16:
         raise ValueError(f"gemm_kq: x must be bf16 on GPU, got {x.dtype}")
     else:
+        if 0 < M <= KQ_TILED_MAX_M and N % 64 == 0:
+            ws = _kq_tiled_ws(M, [(N, K)], scratch, x.device)
+            if ws is not False:
+                if out is None:
+                    out = torch.empty(M, N, dtype=torch.bfloat16,
+                                      device=x.device)
+                _native().gemm_kq_tiled(out, col_off, x, list(planes), bias,
+                                        fmt, ws)
+                return out
         w = dequant_kq(planes, fmt, out=scratch)
     y = torch.nn.functional.linear(x, w, seg_bias)
     if out is None:
         return y
     out[:, col_off:col_off + N] = y
     return out
+
+
+def kq_tiled_splits(N: int, K: int) -> int:
+    """K-split factor (grid.z) the tiled kernel uses for a [N, K] segment:
+    the host's own function, a property of the shape."""
+    return int(_native().kq_tiled_splits(N, K))
+
+
+def _kq_tiled_ws(M: int, shapes, scratch: torch.Tensor | None, device):
+    """The tiled kernel's fp32 workspace for segments of `shapes` [(N, K)]
+    launched one after another on one stream at M rows, sized for the
+    largest KS*M*N among those that split: _wq_tiled_ws's contract (None,
+    a view of `scratch` or a new buffer, False when `scratch` cannot hold
+    it)."""
+    need = 0
+    for N, K in shapes:
+        ks = kq_tiled_splits(N, K)
+        if ks > 1:
+            need = max(need, ks * M * N)
+    if need == 0:
+        return None
+    if scratch is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    if scratch.dtype != torch.bfloat16 or not scratch.is_contiguous() \
+            or scratch.numel() < 2 * need or scratch.data_ptr() % 16:
+        return False
+    return scratch.view(-1)[:2 * need].view(torch.float32)
 
 
 # -- mixture-of-experts routed expert GEMMs (ops/hip/moe.hip) -----------

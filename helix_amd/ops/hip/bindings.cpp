@@ -86,6 +86,11 @@ void dequant_kq(torch::Tensor out, std::vector<torch::Tensor> planes,
                 std::string fmt);
 int64_t kq_kernel_max_m();
 int64_t kq_waves(int64_t N, int64_t K);
+void gemm_kq_tiled(torch::Tensor out, int64_t col_off, torch::Tensor x,
+                   std::vector<torch::Tensor> planes,
+                   c10::optional<torch::Tensor> bias, std::string fmt,
+                   c10::optional<torch::Tensor> ws);
+int64_t kq_tiled_splits(int64_t N, int64_t K);
 void moe_route(torch::Tensor topk_ids, torch::Tensor topk_w,
                torch::Tensor logits);
 void moe_align(torch::Tensor expert_off, torch::Tensor sorted_pairs,
@@ -178,6 +183,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kq_waves", &kq_waves,
         "K-split factor (waves per workgroup) gemm_kq uses for a [N,K] weight");
   m.attr("KQ_KERNEL_MAX_M") = kq_kernel_max_m();
+  m.def("gemm_kq_tiled", &gemm_kq_tiled,
+        "Q4_K/Q6_K weight-only GEMM into out[:, col_off:col_off+N] for any "
+        "M, N % 64 == 0: x tile in LDS, split K (fp32 workspace ws when "
+        "kq_tiled_splits > 1)");
+  m.def("kq_tiled_splits", &kq_tiled_splits,
+        "K-split factor (grid.z) gemm_kq_tiled uses for a [N,K] segment");
   m.def("moe_route", &moe_route,
         "MoE routing: fp32 softmax, top-k (ties to the lower expert), "
         "renormalised weights");

@@ -244,6 +244,10 @@ int kq_fmt(const std::string& fmt) {
   return fmt == "q4_k" ? 4 : 6;
 }
 
+}  // namespace
+
+// Shared with gemm_kq_tiled.hip.
+namespace helix {
 void check_plane(const torch::Tensor& t, const char* name,
                  torch::ScalarType dtype, std::vector<int64_t> shape,
                  const torch::Tensor& first) {
@@ -286,6 +290,9 @@ int64_t check_kq_planes(const std::vector<torch::Tensor>& planes, int fmt,
   *K_out = K;
   return N;
 }
+}  // namespace helix
+
+namespace {
 
 struct KQArgs {
   uint16_t* out;

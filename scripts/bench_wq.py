@@ -47,11 +47,14 @@ def weight_bytes(variant: str, N: int, K: int) -> int:
     return N * K * BYTES_PER_256[variant] // 256
 
 
-def path(variant: str, M: int) -> str:
+def path(variant: str, M: int, N: int) -> str:
     if variant == "bf16":
         return "library"
     if variant in ops.KQ_FORMATS:
-        return "fused" if M <= ops.KQ_FUSED_MAX_M else "dequant+library"
+        if M <= ops.KQ_FUSED_MAX_M:
+            return "fused"
+        tiled = M <= ops.KQ_TILED_MAX_M and N % 64 == 0
+        return "tiled" if tiled else "dequant+library"
     if M <= ops.WQ_FUSED_MAX_M:
         return "fused"
     return "tiled" if M <= ops.WQ_TILED_MAX_M else "dequant+library"
@@ -70,9 +73,9 @@ def main():
                     "the shipped cutoffs (to measure where the cutoff "
                     "belongs)")
     ap.add_argument("--tiled-max-m", type=int, default=-1,
-                    help="time the tiled Q4_0/Q8_0 kernel up to this M "
-                    "instead of the shipped cutoff; 0 forces dequant + "
-                    "library above the fused cutoff")
+                    help="time the tiled kernels (Q4_0/Q8_0 and Q4_K/Q6_K) "
+                    "up to this M instead of the shipped cutoffs; 0 forces "
+                    "dequant + library above the fused cutoff")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default="")
@@ -85,6 +88,7 @@ def main():
         ops.KQ_FUSED_MAX_M = min(args.fused_max_m, ops._C.KQ_KERNEL_MAX_M)
     if args.tiled_max_m >= 0:
         ops.WQ_TILED_MAX_M = args.tiled_max_m
+        ops.KQ_TILED_MAX_M = args.tiled_max_m
     dev = torch.device("cuda:0")
     lines = []
     for shape in args.shape or SHAPES:
@@ -135,7 +139,7 @@ def main():
             for v, ts in times.items():
                 med, mn = statistics.median(ts), min(ts)
                 rec = {"N": N, "K": K, "M": M, "variant": v,
-                       "path": path(v, M),
+                       "path": path(v, M, N),
                        "us_median": round(med, 2), "us_min": round(mn, 2),
                        "weight_bytes": weight_bytes(v, N, K),
                        "weight_GBps": round(

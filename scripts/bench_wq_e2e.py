@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """End-to-end decode rate and resident weight bytes of one engine
 configuration: --model, --batch (= max_num_seqs, all slots busy) and
---quant in {none, q8_0, q4_0}; a mixture-of-experts preset takes
+--quant in {none, q8_0, q4_0, q4_k, q6_k}; a mixture-of-experts preset takes
 --expert-quant in {none, q8_0, q4_0} instead (its experts alone are
 quantised), or q4_k / q6_k / q4_k_m: the model is then built in bf16 on the
 GPU, its experts are quantised layer by layer
@@ -35,7 +35,11 @@ def main():
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--quant", default="none",
-                    choices=["none", "q8_0", "q4_0"])
+                    choices=["none", "q8_0", "q4_0", "q4_k", "q6_k"])
+    ap.add_argument("--tiled-max-m", type=int, default=-1,
+                    help="serve the tiled kernels up to this M instead of "
+                    "the shipped cutoffs; 0 sends every batch above the "
+                    "fused cutoff down dequant + library")
     ap.add_argument("--expert-quant", default="none",
                     choices=["none", "q8_0", "q4_0", "q4_k", "q6_k",
                              "q4_k_m"])
@@ -45,6 +49,9 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_wq_e2e.py needs a GPU")
+    if args.tiled_max_m >= 0:
+        import helix_amd.ops as ops
+        ops.WQ_TILED_MAX_M = ops.KQ_TILED_MAX_M = args.tiled_max_m
     max_len = args.prompt_len + args.warmup + args.steps + 64
     cfg = EngineConfig(
         model=args.model, max_num_seqs=args.batch, max_model_len=max_len,
@@ -84,6 +91,7 @@ def main():
     print(json.dumps({
         "model": args.model, "batch": args.batch, "quant": args.quant,
         "expert_quant": args.expert_quant,
+        "tiled_max_m": args.tiled_max_m,
         "tok_per_s": round(args.batch * args.steps / dt, 1),
         "ms_per_step": round(dt / args.steps * 1e3, 3),
         "model_bytes": model_bytes,
