@@ -358,7 +358,8 @@ class LLMEngine:
         """Admit waiting sequences for prefill. A prompt whose remaining
         tokens exceed max_prefill_tokens is processed in CHUNKS across
         steps: each chunk writes its KV and the next chunk re-enters as
-        a cached-prefix suffix (query-offset kernel + paged gather), so
+        a cached-prefix suffix (ops.attn_prefill_paged reads its context
+        in place from the paged cache), so
         one long prompt never monopolizes a step or blows activation
         memory."""
         batch: List[Sequence] = []
@@ -448,7 +449,6 @@ class LLMEngine:
     def _run_prefill(self, batch: List[Sequence]):
         bs = self.cfg.block_size
         input_ids, positions, slots, cu_q, cu_k = [], [], [], [0], [0]
-        gather_blk, gather_off = [], []
         row_slots = self._lora_slots([s.lora for s in batch])
         tok_slots: List[int] = []
         targets = getattr(self, "_chunk_target", {})
@@ -463,26 +463,31 @@ class LLMEngine:
             cu_k.append(cu_k[-1] + L)
             if row_slots is not None:
                 tok_slots.extend([row_slots[len(cu_q) - 2]] * (L - P))
-            if any_cached:
-                for p in range(L):
-                    gather_blk.append(seq.block_table[p // bs])
-                    gather_off.append(p % bs)
         dev = self.device
+        paged = {}
+        if any_cached:
+            # the context is read in place through the batch's rows of the
+            # persistent table (_assign_row filled them when the sequences
+            # were scheduled), cut to the longest context: one H2D copy
+            klens = np.diff(np.asarray(cu_k, dtype=np.int32))
+            max_klen = int(klens.max())
+            rows = [s.row for s in batch]
+            paged = dict(
+                cu_seqlens_k=torch.tensor(cu_k, dtype=torch.int32, device=dev),
+                block_tables=torch.from_numpy(
+                    self._bt_np[rows, :(max_klen + bs - 1) // bs]).to(dev),
+                seq_lens=torch.from_numpy(klens).to(dev),
+                max_klen=max_klen)
         meta = PrefillMeta(
             cu_seqlens=torch.tensor(cu_q, dtype=torch.int32, device=dev),
             max_seqlen=max(targets.get(s.seq_id, len(s.prompt_ids))
                            - s.cached_prefix for s in batch),
             slot_mapping=torch.tensor(slots, dtype=torch.int64, device=dev),
             positions=torch.tensor(positions, dtype=torch.int64, device=dev),
-            cu_seqlens_k=(torch.tensor(cu_k, dtype=torch.int32, device=dev)
-                          if any_cached else None),
-            gather_blk=(torch.tensor(gather_blk, dtype=torch.int64,
-                                     device=dev) if any_cached else None),
-            gather_off=(torch.tensor(gather_off, dtype=torch.int64,
-                                     device=dev) if any_cached else None),
             lora_slots=(torch.tensor(tok_slots, dtype=torch.int32,
                                      device=dev)
-                        if row_slots is not None else None))
+                        if row_slots is not None else None),
+            **paged)
         ids = torch.tensor(input_ids, dtype=torch.int64, device=dev)
         hidden = self.model(ids, self.kv.caches, meta)
         # register this batch's newly COMPLETED full blocks in the

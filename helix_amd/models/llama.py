@@ -154,16 +154,18 @@ def get_preset(name: str) -> LlamaConfig:
 @dataclass
 class PrefillMeta:
     """Varlen prefill: q/k/v are concatenated new tokens of all sequences.
-    With prefix caching, q covers only the uncached suffix; attention
-    gathers the full context K/V from the paged cache (gather_blk/off)
-    and cu_seqlens_k carries the full-context boundaries."""
+    With prefix caching or chunking, q covers only the uncached suffix;
+    attention reads the full context K/V from the paged cache through
+    block_tables / seq_lens (ops.attn_prefill_paged). cu_seqlens_k, the
+    full-context boundaries, is set exactly on such a step."""
     cu_seqlens: torch.Tensor       # [B+1] int32 (new-token boundaries)
     max_seqlen: int
     slot_mapping: torch.Tensor     # [T] int64 cache slots for new tokens
     positions: torch.Tensor        # [T] int64
     cu_seqlens_k: Optional[torch.Tensor] = None   # [B+1] int32 full context
-    gather_blk: Optional[torch.Tensor] = None     # [Tk] int64
-    gather_off: Optional[torch.Tensor] = None     # [Tk] int64
+    block_tables: Optional[torch.Tensor] = None   # [B, cols] int32
+    seq_lens: Optional[torch.Tensor] = None       # [B] int32 full context
+    max_klen: int = 0                             # host-side max(seq_lens)
     is_prefill: bool = True
     lora_slots: Optional[torch.Tensor] = None     # [T] int32, -1 = none
 
@@ -244,18 +246,14 @@ class Attention(nn.Module):
             eps=self.eps if self.q_norm_w is not None else 0.0)
         if meta.is_prefill:
             if meta.cu_seqlens_k is not None:
-                # cached-prefix prefill: full-context K/V gathered from
-                # the paged cache (new tokens were just written above)
+                # cached-prefix prefill: full-context K/V read in place
+                # from the paged cache (new tokens were just written above)
                 k_cache, v_cache = kv_cache
-                k_all = k_cache[meta.gather_blk, :, meta.gather_off]
-                v_all = v_cache[meta.gather_blk, :, meta.gather_off]
-                if k_all.dtype == torch.uint8:      # fp8 KV cache
-                    k_all = ops.kv_fp8_dequant(k_all, q.dtype)
-                    v_all = ops.kv_fp8_dequant(v_all, q.dtype)
-                o = ops.attn_prefill(q, k_all, v_all, meta.cu_seqlens,
-                                     meta.max_seqlen, self.scale,
-                                     window=self.window,
-                                     cu_seqlens_k=meta.cu_seqlens_k)
+                o = ops.attn_prefill_paged(q, k_cache, v_cache,
+                                           meta.block_tables,
+                                           meta.cu_seqlens, meta.seq_lens,
+                                           meta.max_seqlen, meta.max_klen,
+                                           self.scale, window=self.window)
             else:
                 o = ops.attn_prefill(q, k, v, meta.cu_seqlens,
                                      meta.max_seqlen, self.scale,

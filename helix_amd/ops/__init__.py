@@ -202,6 +202,33 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             window, cu_seqlens_k)
 
 
+def attn_prefill_paged(q: torch.Tensor, k_cache: torch.Tensor,
+                       v_cache: torch.Tensor, block_tables: torch.Tensor,
+                       cu_seqlens: torch.Tensor, seq_lens: torch.Tensor,
+                       max_seqlen: int, max_klen: int, scale: float,
+                       window: int = 0) -> torch.Tensor:
+    """Causal varlen attention of query suffixes over the paged KV cache
+    (prefix-cached and chunked prefill). q [T, Hq, D] holds the last
+    cu_seqlens[b+1] - cu_seqlens[b] tokens of each sequence; its context of
+    seq_lens[b] tokens (the suffix included, so seq_lens[b] >= that count: a
+    precondition, asserted on CPU only) is read from k_cache / v_cache
+    [num_blocks, Hkv, block_size, D], bf16 or e4m3 bytes (uint8), through
+    block_tables [B, cols] int32. max_seqlen is the longest suffix,
+    max_klen the longest context (host ints: no sync, no allocation beyond
+    the output). GPU: one kernel (attn_prefill_paged.hip), bit-identical
+    to attn_prefill on the gathered, dequantized K/V. CPU: exactly that
+    composition."""
+    if q.is_cuda:
+        out = torch.empty_like(q)
+        _native().attn_prefill_paged(out, q, k_cache, v_cache, block_tables,
+                                     cu_seqlens, seq_lens, max_seqlen,
+                                     max_klen, scale, window)
+        return out
+    return ref.attn_prefill_paged(q, k_cache, v_cache, block_tables,
+                                  cu_seqlens, seq_lens, max_seqlen, scale,
+                                  window)
+
+
 # Flash-decoding split-K quantum: PART_QUANT in paged_attn_decode.hip,
 # which the extension exports as _C.DECODE_PART_QUANT (a test holds the
 # two equal).

@@ -45,6 +45,11 @@ void attn_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor k,
                   torch::Tensor v, torch::Tensor cu_seqlens,
                   torch::Tensor cu_seqlens_k, int64_t max_seqlen,
                   double scale, bool causal, int64_t window);
+void attn_prefill_paged(torch::Tensor out, torch::Tensor q,
+                        torch::Tensor k_cache, torch::Tensor v_cache,
+                        torch::Tensor block_tables, torch::Tensor cu_seqlens,
+                        torch::Tensor seq_lens, int64_t max_seqlen,
+                        int64_t max_klen, double scale, int64_t window);
 void sample_tokens(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperatures, torch::Tensor seeds);
 void sample_tokens_ext(torch::Tensor out, torch::Tensor logits,
@@ -153,6 +158,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("DECODE_PART_QUANT") = decode_part_quant();
   m.def("attn_prefill", &attn_prefill,
         "Varlen causal flash prefill attention (MFMA)");
+  m.def("attn_prefill_paged", &attn_prefill_paged,
+        "Varlen causal flash prefill attention over the paged KV cache "
+        "(bf16 or e4m3), K/V read through the block table");
   m.def("sample_tokens", &sample_tokens, "Greedy/Gumbel token sampling");
   m.def("sample_tokens_ext", &sample_tokens_ext,
         "Fused top-k/top-p/penalty Gumbel sampling (histogram threshold)");

@@ -507,6 +507,21 @@ void launch_decode(uint16_t* out, float* tmp_out, float* tmp_ml,
 
 int64_t decode_part_quant() { return PART_QUANT; }
 
+namespace helix {
+// The rule a cache block size obeys, for every kernel that reads the paged
+// cache (attn_prefill_paged.hip too): they address a token with shift and
+// mask, and a decode chunk's block ids have IDS_MAX slots in LDS. Returns
+// log2(block_size).
+int kv_block_log2(int64_t block_size) {
+  TORCH_CHECK(block_size >= MIN_BS && (block_size & (block_size - 1)) == 0,
+              "KV cache block_size must be a power of two and at least ",
+              MIN_BS, ", got ", block_size);
+  int bs_log2 = 0;
+  while ((int64_t(1) << bs_log2) < block_size) ++bs_log2;
+  return bs_log2;
+}
+}  // namespace helix
+
 void paged_attn_decode(torch::Tensor out, torch::Tensor q,
                        torch::Tensor k_cache, torch::Tensor v_cache,
                        torch::Tensor block_tables, torch::Tensor seq_lens,
@@ -525,13 +540,7 @@ void paged_attn_decode(torch::Tensor out, torch::Tensor q,
   const int G = Hq / Hkv;
   TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "G must be 1/2/4/8");
   TORCH_CHECK(max_len >= 1, "max_len must be >= 1, got ", max_len);
-  // the kernel addresses a token with shift and mask, and a chunk's
-  // block ids have IDS_MAX slots in LDS
-  TORCH_CHECK(block_size >= MIN_BS && (block_size & (block_size - 1)) == 0,
-              "KV cache block_size must be a power of two and at least ",
-              MIN_BS, ", got ", block_size);
-  int bs_log2 = 0;
-  while ((1 << bs_log2) < block_size) ++bs_log2;
+  const int bs_log2 = helix::kv_block_log2(block_size);
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
                   out.scalar_type() == torch::kBFloat16,
               "q and out must be bf16");

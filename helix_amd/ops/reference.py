@@ -157,6 +157,34 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return out
 
 
+def attn_prefill_paged(q: torch.Tensor, k_cache: torch.Tensor,
+                       v_cache: torch.Tensor, block_tables: torch.Tensor,
+                       cu_seqlens: torch.Tensor, seq_lens: torch.Tensor,
+                       max_seqlen: int, scale: float,
+                       window: int = 0) -> torch.Tensor:
+    """attn_prefill on each sequence's first seq_lens[b] cache tokens,
+    gathered through its block-table row; an e4m3 (uint8) cache is
+    dequantized to q's dtype after the gather."""
+    bs = k_cache.shape[2]
+    qlens = (cu_seqlens[1:] - cu_seqlens[:-1]).tolist()
+    klens = [int(n) for n in seq_lens]
+    assert all(kl >= ql for kl, ql in zip(klens, qlens)), \
+        "attn_prefill_paged: a context shorter than its query suffix"
+    blk, off = [], []
+    for b, n in enumerate(klens):
+        pos = torch.arange(n)
+        blk.append(block_tables[b, pos // bs].long())
+        off.append(pos % bs)
+    blk, off = torch.cat(blk), torch.cat(off)
+    k, v = k_cache[blk, :, off], v_cache[blk, :, off]
+    if k.dtype == torch.uint8:
+        k = k.view(torch.float8_e4m3fn).to(q.dtype)
+        v = v.view(torch.float8_e4m3fn).to(q.dtype)
+    cu_k = torch.tensor([0] + klens).cumsum(0).int()
+    return attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale, True, window,
+                        cu_k)
+
+
 def paged_attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
                       v_cache: torch.Tensor, block_tables: torch.Tensor,
                       seq_lens: torch.Tensor, scale: float,
