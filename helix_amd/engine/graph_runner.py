@@ -84,6 +84,7 @@ class CUDAGraphRunner:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
+                meta.lora_groups = None
                 hidden = self.model(ids, self.kv_caches, meta)
                 logits = self.model.compute_logits(hidden)
         torch.cuda.current_stream().wait_stream(s)
@@ -92,6 +93,9 @@ class CUDAGraphRunner:
         g = torch.cuda.CUDAGraph()
         ctx = (torch.cuda.graph(g, pool=self.pool) if self.pool is not None
                else torch.cuda.graph(g))
+        # the row grouping of a large LoRA batch (models/llama.py::_lora) is
+        # one node of the graph: the warm-up's groups must not be reused
+        meta.lora_groups = None
         with ctx:
             hidden = self.model(ids, self.kv_caches, meta)
             logits = self.model.compute_logits(hidden)

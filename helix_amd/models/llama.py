@@ -168,6 +168,7 @@ class PrefillMeta:
     max_klen: int = 0                             # host-side max(seq_lens)
     is_prefill: bool = True
     lora_slots: Optional[torch.Tensor] = None     # [T] int32, -1 = none
+    lora_groups: Optional[tuple] = None   # ops.lora_group, set by _lora
 
 
 @dataclass
@@ -181,6 +182,7 @@ class DecodeMeta:
     workspace: Optional[tuple] = None
     is_prefill: bool = False
     lora_slots: Optional[torch.Tensor] = None     # [B] int32, -1 = none
+    lora_groups: Optional[tuple] = None   # ops.lora_group, set by _lora
 
 
 class HLinear(nn.Linear):
@@ -202,7 +204,16 @@ def _lora(out: torch.Tensor, x: torch.Tensor, lora, proj: str, meta):
     A, B, n_off = lora.stacks[proj]
     if not out.is_contiguous():
         out = out.contiguous()
-    return ops.lora_apply(out, x, A, B, slots, lora.scale, n_off)
+    # from LORA_SGMV_MIN_T rows on, the rows are grouped by slot once per
+    # forward (the first projection fills meta.lora_groups) and every
+    # projection runs the segment-tiled kernels
+    groups = getattr(meta, "lora_groups", None)
+    if groups is None and x.is_cuda \
+            and slots.shape[0] >= ops.LORA_SGMV_MIN_T \
+            and A.shape[0] <= ops.LORA_SGMV_MAX_S:
+        groups = meta.lora_groups = ops.lora_group(slots, A.shape[0])
+    return ops.lora_apply(out, x, A, B, slots, lora.scale, n_off,
+                          groups=groups)
 
 
 class Attention(nn.Module):

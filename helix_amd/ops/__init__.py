@@ -1078,12 +1078,60 @@ def lora_expand(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
     return ref.lora_expand(out, y, B, slot, scale, n_off)
 
 
+# Row count from which models/llama.py groups the rows by slot and
+# lora_apply runs the segment-tiled MFMA kernels (lora_sgmv.hip) instead of
+# the per-token ones. One plus a member of graph_runner.BATCH_BUCKETS, so a
+# batch and its padded bucket take the same path (the WQ_FUSED_MAX_M rule);
+# measured in profiles/r15_lora_sgmv.md.
+LORA_SGMV_MIN_T = 513
+LORA_SGMV_MAX_S = 256
+
+
+def lora_group(slot: torch.Tensor, S: int):
+    """(seg_off [S+1] int32, rows [T] int32): the rows of slot s are
+    rows[seg_off[s]:seg_off[s+1]], ascending; a row whose slot is outside
+    [0, S) is in no list. On the GPU this is moe_align with k = 1 (no sync,
+    capture-safe), which serves S <= 256."""
+    if slot.dim() != 1 or slot.dtype != torch.int32:
+        raise ValueError("lora_group: slot must be a 1-D int32 tensor")
+    if S < 1 or S > LORA_SGMV_MAX_S:
+        raise ValueError(f"lora_group: S ({S}) must be in "
+                         f"[1, {LORA_SGMV_MAX_S}]")
+    return moe_align(slot.view(-1, 1), S)
+
+
+def lora_sgmv_shrink(y: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                     groups) -> torch.Tensor:
+    """lora_shrink over grouped rows (GPU only): y[t] = A[s] @ x[t] in fp32
+    for every row t in the list of a slot s. groups = lora_group(slot, S)."""
+    _native().lora_sgmv_shrink(y, x, A, groups[0], groups[1])
+    return y
+
+
+def lora_sgmv_expand(out: torch.Tensor, y: torch.Tensor, B: torch.Tensor,
+                     groups, scale: torch.Tensor, n_off) -> torch.Tensor:
+    """lora_expand over grouped rows (GPU only), in place. Slice boundaries
+    must be multiples of 16."""
+    _native().lora_sgmv_expand(out, y, B, groups[0], groups[1], scale,
+                               [int(v) for v in n_off])
+    return out
+
+
 def lora_apply(out: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
                B: torch.Tensor, slot: torch.Tensor, scale: torch.Tensor,
-               n_off) -> torch.Tensor:
+               n_off, groups=None) -> torch.Tensor:
     """Shrink + expand: adds each row's adapter delta into `out` in place.
-    Rows with no adapter (slot outside [0, S)) keep `out` bit-identical."""
-    y = torch.empty(x.shape[0], A.shape[1], dtype=torch.float32,
-                    device=x.device)
+    Rows with no adapter (slot outside [0, S)) keep `out` bit-identical.
+    With groups = lora_group(slot, S) on the GPU, and K % 32 == 0, S <= 256
+    and every slice boundary a multiple of 16, the segment-tiled MFMA
+    kernels run; otherwise the per-token ones. On the CPU `groups` changes
+    nothing."""
+    T = x.shape[0]
+    y = torch.empty(T, A.shape[1], dtype=torch.float32, device=x.device)
+    if groups is not None and x.is_cuda and x.shape[1] % 32 == 0 \
+            and A.shape[0] <= LORA_SGMV_MAX_S \
+            and all(int(v) % 16 == 0 for v in n_off):
+        lora_sgmv_shrink(y, x, A, groups)
+        return lora_sgmv_expand(out, y, B, groups, scale, n_off)
     lora_shrink(y, x, A, slot)
     return lora_expand(out, y, B, slot, scale, n_off)

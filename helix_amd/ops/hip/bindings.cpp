@@ -74,6 +74,11 @@ void lora_shrink(torch::Tensor y, torch::Tensor x, torch::Tensor A,
 void lora_expand(torch::Tensor out, torch::Tensor y, torch::Tensor B,
                  torch::Tensor slot, torch::Tensor scale,
                  std::vector<int64_t> n_off);
+void lora_sgmv_shrink(torch::Tensor y, torch::Tensor x, torch::Tensor A,
+                      torch::Tensor seg_off, torch::Tensor rows);
+void lora_sgmv_expand(torch::Tensor out, torch::Tensor y, torch::Tensor B,
+                      torch::Tensor seg_off, torch::Tensor rows,
+                      torch::Tensor scale, std::vector<int64_t> n_off);
 void gemm_wq(torch::Tensor out, torch::Tensor x, torch::Tensor qs,
              torch::Tensor d, c10::optional<torch::Tensor> bias,
              int64_t bits);
@@ -173,6 +178,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Multi-LoRA shrink: y[t] = A[slot[t]] @ x[t] (fp32 out)");
   m.def("lora_expand", &lora_expand,
         "Multi-LoRA expand: out[t] += scale[s] * B[s] @ y[t] (in place)");
+  m.def("lora_sgmv_shrink", &lora_sgmv_shrink,
+        "Multi-LoRA shrink over rows grouped by slot (16-row MFMA tiles)");
+  m.def("lora_sgmv_expand", &lora_sgmv_expand,
+        "Multi-LoRA expand over rows grouped by slot (16-row MFMA tiles)");
   m.def("gemm_wq", &gemm_wq,
         "Q4_0/Q8_0 weight-only GEMM, dequant fused into the MFMA loop (M <= 64)");
   m.def("dequant_wq", &dequant_wq,

@@ -2,12 +2,15 @@
 """Multi-LoRA cost on an MI355X: kernel pair, decode step, prefill.
 
   kernels  us per shrink+expand pair at Llama-3-8B projection shapes, timed
-           with device events. Run it once more under
+           with device events: the per-token pair, the segment-tiled pair
+           (lora_sgmv.hip) and the row grouping, interleaved; with --ts it
+           also derives ops.LORA_SGMV_MIN_T. Run it once more under
            `rocprofv3 --kernel-trace --stats --output-format csv -d DIR --`
            and feed the trace to `report` for per-kernel times.
   report   per-config kernel times + achieved bytes/s from a kernel trace.
   steps    ms/step of llama3-8b decode with max_loras=0, max_loras=4 with
-           no row using an adapter, and max_loras=4 round-robin, the
+           no row using an adapter, and max_loras=4 round-robin on the
+           per-token kernels and on the shipped dispatch, the
            configurations alternating inside one process; plus prefill
            time for 8 x 1024-token prompts with and without adapters.
 
@@ -27,7 +30,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-S = 4                                    # adapter slots in the stacks
+S = 4                                    # adapter slots ("distinct": 64)
 # Llama-3-8B projections: name -> (K, slice widths)
 SHAPES = {
     "qkv": (4096, (4096, 1024, 1024)),
@@ -35,12 +38,16 @@ SHAPES = {
     "gate_up": (4096, (14336, 14336)),
     "down": (14336, (4096,)),
 }
-PATTERNS = ("one", "rr4", "none")
+PATTERNS = ("one", "rr4", "distinct", "none")
 
 
-def configs():
+def n_slots(pattern: str, T: int) -> int:
+    return min(T, 64) if pattern == "distinct" else S
+
+
+def configs(ts=(64, 512)):
     for name, (K, widths) in SHAPES.items():
-        for T in (64, 512):
+        for T in ts:
             for r in (16, 64):
                 for pat in PATTERNS:
                     yield {"proj": name, "K": K, "widths": list(widths),
@@ -50,7 +57,8 @@ def configs():
 def algorithmic_bytes(c) -> int:
     """x + the A slice and B of every distinct slot + out read and written
     (what the pair must move once; y and the slot vector are left out)."""
-    n_distinct = {"one": 1, "rr4": 4, "none": 0}[c["pattern"]]
+    n_distinct = {"one": 1, "rr4": 4, "none": 0,
+                  "distinct": min(c["T"], 64)}[c["pattern"]]
     if n_distinct == 0:
         return 0
     N, ns = sum(c["widths"]), len(c["widths"])
@@ -63,6 +71,8 @@ def slot_vector(pattern: str, T: int) -> torch.Tensor:
         v = [1] * T
     elif pattern == "rr4":
         v = [t % 4 for t in range(T)]
+    elif pattern == "distinct":
+        v = [t % 64 for t in range(T)]
     else:
         v = [-1] * T
     return torch.tensor(v, dtype=torch.int32, device="cuda")
@@ -75,54 +85,93 @@ def need_gpu():
     return ops
 
 
+def time_us(fn, warmup: int, iters: int) -> float:
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1000.0 / iters
+
+
 def cmd_kernels(args):
     ops = need_gpu()
     torch.manual_seed(0)
     rows = []
-    for c in configs():
+    for c in configs(args.ts):
         K, widths, T, r = c["K"], c["widths"], c["T"], c["r"]
         N, ns = sum(widths), len(widths)
+        S_ = n_slots(c["pattern"], T)
         n_off = [0]
         for w in widths:
             n_off.append(n_off[-1] + w)
         x = torch.randn(T, K, device="cuda").bfloat16()
-        A = (torch.randn(S, ns * r, K, device="cuda") / K ** 0.5).bfloat16()
-        B = (torch.randn(S, N, r, device="cuda") / r ** 0.5).bfloat16()
+        A = (torch.randn(S_, ns * r, K, device="cuda") / K ** 0.5).bfloat16()
+        B = (torch.randn(S_, N, r, device="cuda") / r ** 0.5).bfloat16()
         out = torch.randn(T, N, device="cuda").bfloat16()
         y = torch.empty(T, ns * r, device="cuda")
-        scale = torch.full((S,), 0.01, device="cuda")
+        scale = torch.full((S_,), 0.01, device="cuda")
         slot = slot_vector(c["pattern"], T)
+        groups = ops.lora_group(slot, S_)
 
         def pair():
             ops.lora_shrink(y, x, A, slot)
             ops.lora_expand(out, y, B, slot, scale, n_off)
 
-        for _ in range(args.warmup):
-            pair()
-        torch.cuda.synchronize()
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            pair()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1000.0 / args.iters
+        def sgmv_pair():
+            ops.lora_sgmv_shrink(y, x, A, groups)
+            ops.lora_sgmv_expand(out, y, B, groups, scale, n_off)
+
+        # per-token, segment-tiled, per-token, segment-tiled: the mean of
+        # each variant's two interleaved measurements
+        t = [time_us(f, args.warmup, args.iters)
+             for f in (pair, sgmv_pair, pair, sgmv_pair)]
+        us, sg = (t[0] + t[2]) / 2, (t[1] + t[3]) / 2
+        grp = time_us(lambda: ops.lora_group(slot, S_), args.warmup,
+                      args.iters)
         nbytes = algorithmic_bytes(c)
         rows.append({**c, "pair_us_events": round(us, 2),
+                     "sgmv_pair_us_events": round(sg, 2),
+                     "group_us_events": round(grp, 2),
                      "alg_bytes": nbytes,
                      "alg_TBps_events": (round(nbytes / us / 1e6, 3)
-                                         if nbytes else None)})
+                                         if nbytes else None),
+                     "sgmv_alg_TBps_events": (round(nbytes / sg / 1e6, 3)
+                                              if nbytes else None)})
         print(json.dumps(rows[-1]), flush=True)
+    # cutoff: the smallest T from which, at every projection, rank and
+    # pattern, the new pair plus a quarter of the grouping (charged once to
+    # a layer's four pairs) is not slower than the per-token pair
+    losing = {}
+    for r_ in rows:
+        if r_["pattern"] != "none" and r_["sgmv_pair_us_events"] \
+                + r_["group_us_events"] / 4 > r_["pair_us_events"]:
+            losing.setdefault(r_["T"], []).append(
+                (r_["proj"], r_["r"], r_["pattern"]))
+    ok_from = None
+    for T in sorted(set(args.ts), reverse=True):
+        if T in losing:
+            break
+        ok_from = T
+    print(json.dumps({"sgmv_not_slower_from_T": ok_from,
+                      "losing": {str(k): v for k, v in losing.items()}}),
+          flush=True)
     os.makedirs(args.out, exist_ok=True)
     with open(os.path.join(args.out, "lora_kernels_events.json"), "w") as f:
         json.dump({"warmup": args.warmup, "iters": args.iters,
-                   "rows": rows}, f, indent=1)
+                   "sgmv_not_slower_from_T": ok_from, "rows": rows}, f,
+                  indent=1)
 
 
 def cmd_report(args):
-    """The kernels run launches, per config and in order, (warmup + iters)
-    shrink kernels and as many expand kernels; cut the trace accordingly."""
+    """The kernels run launches, per config and in order, two rounds of
+    (warmup + iters) per-token shrink kernels and as many expand kernels;
+    cut the trace accordingly (the first round is reported)."""
     paths = glob.glob(os.path.join(args.trace_dir, "**",
                                    "*kernel_trace.csv"), recursive=True)
     if not paths:
@@ -139,7 +188,7 @@ def cmd_report(args):
             if f"lora_{k}_kernel" in name:
                 dur[k].append((int(r["End_Timestamp"])
                                - int(r["Start_Timestamp"])) / 1000.0)
-    per = args.warmup + args.iters
+    per = 2 * (args.warmup + args.iters)
     cfgs = list(configs())
     for k in dur:
         if len(dur[k]) != per * len(cfgs):
@@ -147,8 +196,8 @@ def cmd_report(args):
                      f"{per * len(cfgs)} (same --warmup/--iters?)")
     rows = []
     for i, c in enumerate(cfgs):
-        sh = dur["shrink"][i * per + args.warmup:(i + 1) * per]
-        ex = dur["expand"][i * per + args.warmup:(i + 1) * per]
+        first = slice(i * per + args.warmup, i * per + per // 2)
+        sh, ex = dur["shrink"][first], dur["expand"][first]
         sh_us, ex_us = sum(sh) / len(sh), sum(ex) / len(ex)
         nbytes = algorithmic_bytes(c)
         rows.append({**c, "shrink_us": round(sh_us, 2),
@@ -202,6 +251,7 @@ def cmd_steps(args):
     # hooks are no-ops, so the max_loras=0 engine runs the base sequence.
     eng0 = engine(0)
     eng4 = engine(4)
+    eng4_tok = engine(4)                 # the per-token kernels at every T
     names = [f"a{i}" for i in range(4)]
     with tempfile.TemporaryDirectory() as d:
         for i, n in enumerate(names):
@@ -210,13 +260,20 @@ def cmd_steps(args):
             L.save_peft_adapter(os.path.join(d, n), t, r=args.rank,
                                 lora_alpha=args.rank)
             eng4.add_lora(n, os.path.join(d, n))
+            eng4_tok.add_lora(n, os.path.join(d, n))
     sp = SamplingParams(temperature=0.0, max_tokens=10 ** 9, ignore_eos=True)
     gen = torch.Generator().manual_seed(1234)
     run_no = [0]
 
+    import helix_amd.ops as ops
+    shipped_min_t = ops.LORA_SGMV_MIN_T
+
     def measure(eng, B, plen, loras, steps, warmup):
         """-> (prefill_s, ms_per_step)."""
         run_no[0] += 1
+        # the per-token engine never groups rows (its graphs are captured
+        # inside this call, so they hold the per-token kernels)
+        ops.LORA_SGMV_MIN_T = 1 << 30 if eng is eng4_tok else shipped_min_t
         prompts = torch.randint(3, mcfg.vocab_size - 1, (B, plen),
                                 generator=gen).tolist()
         ids = [f"r{run_no[0]}-{i}" for i in range(B)]
@@ -245,6 +302,8 @@ def cmd_steps(args):
 
     variants = [("max_loras=0", eng0, None),
                 ("max_loras=4, no adapter rows", eng4, None),
+                ("max_loras=4, round-robin, per-token kernels", eng4_tok,
+                 names),
                 ("max_loras=4, round-robin", eng4, names)]
     res = {"model": args.model, "rank": args.rank,
            "prompt_len": args.prompt_len, "steps": args.steps,
@@ -282,6 +341,9 @@ def main():
     k = sub.add_parser("kernels")
     k.add_argument("--iters", type=int, default=20)
     k.add_argument("--warmup", type=int, default=3)
+    k.add_argument("--ts", type=int, nargs="+", default=[64, 512],
+                   help="row counts (the cutoff derivation uses one plus "
+                        "each batch bucket)")
     r = sub.add_parser("report")
     r.add_argument("trace_dir")
     r.add_argument("--iters", type=int, default=20)
