@@ -641,13 +641,41 @@ def _kq_tiled_ws(M: int, shapes, scratch: torch.Tensor | None, device):
 # -- mixture-of-experts routed expert GEMMs (ops/hip/moe.hip) -----------
 # Largest T at which moe_experts(fused=None) takes the fused kernels; above
 # it the eager library path runs (one host sync, so never under capture;
-# decode passes fused=True). The rule: the largest benchmarked T at which
+# decode passes fused=True) until the grouped prefill kernels take over
+# (MOE_GROUPED_MIN_T below). The rule: the largest benchmarked T at which
 # the fused path is not slower than the library path on uniform routing, in
 # two runs of scripts/bench_moe.py (T = 1, 8, 16, 64, 128, 512).
 # MEASURED, not the placeholder of 64 (profiles/r08_moe.md): fused over
 # library on uniform routing 2.2x at T = 1, 1.4x at 64, 1.1x at 128 and
 # 0.47x at 512 in both runs.
 MOE_FUSED_MAX_T = 128
+
+# Where moe_experts(fused=None) takes the grouped prefill kernels
+# (ops/hip/moe_grouped.hip; no host sync, capture-safe). The rule for
+# MOE_GROUPED_MIN_T: the smallest benchmarked T (scripts/bench_moe.py, T =
+# 128, 192, 256, 384, 512, 1024, 2048, 4096), never below 193, from which the
+# grouped path is not slower than both other paths on uniform routing, on the
+# Mixtral (E 8) and the Qwen3-30B-A3B (E 128) layer, in two runs; plus one if
+# that T is a member of graph_runner.BATCH_BUCKETS (LORA_SGMV_MIN_T's rule),
+# so that no bucket changes path. 193 keeps the value above the 129- and
+# 135-token prefills that tests pin to the library path.
+# MEASURED, not the provisional 513 (profiles/r16_moe_grouped.md), grouped
+# over library / over fused on uniform routing, the same in both runs:
+#   T        192   256   384   512   1024  2048  4096
+#   Mixtral  1.59  1.51  1.54  1.13  0.87  0.78  0.63   / 1.7 - 3.3
+#   Qwen3    33    31    28    26    19    11.5  6.5    / 1.1 - 1.8
+# 256 is a bucket, so 257. The rule does NOT hold upwards on the Mixtral
+# layer: from T = 1024 its eight per-expert library GEMMs have 256 rows or
+# more and run at 480-830 TF, where the grouped kernel stays at 420-530 TF.
+# So the window is closed at MOE_GROUPED_MAX_T = 512, the largest benchmarked
+# T at which grouped is not slower on both layers, for every layer with fewer
+# than MOE_GROUPED_ANY_T_MIN_E = 128 experts, the one expert count at which
+# grouped was measured ahead at every T (the library path there is a
+# thousand launches per call). Expert counts between 8 and 128 were not
+# measured and keep the library path above 512 tokens, as before.
+MOE_GROUPED_MIN_T = 257
+MOE_GROUPED_MAX_T = 512
+MOE_GROUPED_ANY_T_MIN_E = 128
 
 
 def moe_waves(N: int, K: int, gated: bool) -> int:
@@ -697,7 +725,8 @@ def moe_combine(ypair: torch.Tensor, k: int,
 
 def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
                 topk_ids: torch.Tensor, topk_w: torch.Tensor,
-                fused: bool | None = None, out: torch.Tensor | None = None,
+                fused: bool | str | None = None,
+                out: torch.Tensor | None = None,
                 act: torch.Tensor | None = None,
                 ypair: torch.Tensor | None = None) -> torch.Tensor:
     """Routed SwiGLU experts: out[t] = sum_j topk_w[t, j] *
@@ -707,12 +736,16 @@ def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     sum is unspecified).
     GPU, fused=True: moe_align + the two routed GEMM kernels + moe_combine;
     no host sync, no host-sized shape, no memset, so always capture-safe,
-    and correct for any T. GPU, fused=False: the eager library path (one
-    host sync): x gathered by list, per-expert F.linear / silu_and_mul /
-    F.linear, scaled into the same fp32 ypair, the same moe_combine.
-    fused=None: fused up to MOE_FUSED_MAX_T tokens. `out` [T, H] bf16, `act`
-    [T*k, I] bf16 and `ypair` [T*k, H] fp32 are allocated when None.
-    CPU: the torch reference."""
+    and correct for any T. GPU, fused="grouped": the same with the two
+    grouped prefill kernels (moe_grouped.hip) in place of the routed ones;
+    equally capture-safe and correct for any T. GPU, fused=False: the eager
+    library path (one host sync): x gathered by list, per-expert F.linear /
+    silu_and_mul / F.linear, scaled into the same fp32 ypair, the same
+    moe_combine. fused=None: fused up to MOE_FUSED_MAX_T tokens, grouped
+    from MOE_GROUPED_MIN_T tokens (up to MOE_GROUPED_MAX_T tokens when E <
+    MOE_GROUPED_ANY_T_MIN_E), the library path otherwise. `out` [T, H]
+    bf16, `act` [T*k, I] bf16 and `ypair` [T*k, H] fp32 are allocated when
+    None. CPU: the torch reference, whatever `fused` says."""
     if not x.is_cuda:
         return ref.moe_experts(x, w13, w2, topk_ids, topk_w)
     if x.dim() != 2 or topk_ids.dim() != 2:
@@ -725,7 +758,14 @@ def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
             f"moe_experts: x {tuple(x.shape)}, topk_ids {tuple(topk_ids.shape)}"
             f" and topk_w {tuple(topk_w.shape)} disagree on [T, k]")
     if fused is None:
-        fused = T <= MOE_FUSED_MAX_T
+        if T >= MOE_GROUPED_MIN_T and (T <= MOE_GROUPED_MAX_T
+                                       or E >= MOE_GROUPED_ANY_T_MIN_E):
+            fused = "grouped"
+        else:
+            fused = T <= MOE_FUSED_MAX_T
+    if fused not in (True, False, "grouped"):
+        raise ValueError(f"moe_experts: fused must be True, False, "
+                         f"'grouped' or None, got {fused!r}")
     if act is None:
         act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
     if ypair is None:
@@ -736,7 +776,10 @@ def moe_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
     pairs = torch.empty(P, dtype=torch.int32, device=x.device)
     C.moe_align(off, pairs, topk_ids, E)
-    if fused:
+    if fused == "grouped":
+        C.moe_grouped_gated(act, x, w13, off, pairs, k)
+        C.moe_grouped_down(ypair, act, w2, topk_w, off, pairs)
+    elif fused:
         C.moe_gemm_gated(act, x, w13, off, pairs, k)
         C.moe_gemm_down(ypair, act, w2, topk_w, off, pairs)
     else:
@@ -768,7 +811,7 @@ def moe_forward(x: torch.Tensor, router_logits: torch.Tensor,
                 w13: torch.Tensor, w2: torch.Tensor, k: int,
                 fused: bool | None = None) -> torch.Tensor:
     """One MoE MLP: route (moe_route) and run the routed experts
-    (moe_experts)."""
+    (moe_experts; `fused` is passed through)."""
     ids, w = moe_route(router_logits, k)
     return moe_experts(x, w13, w2, ids, w, fused=fused)
 

@@ -112,6 +112,12 @@ void moe_gemm_down(torch::Tensor ypair, torch::Tensor act, torch::Tensor w2,
                    torch::Tensor topk_w, torch::Tensor expert_off,
                    torch::Tensor sorted_pairs);
 void moe_combine(torch::Tensor out, torch::Tensor ypair, int64_t k);
+void moe_grouped_gated(torch::Tensor act, torch::Tensor x, torch::Tensor w13,
+                       torch::Tensor expert_off, torch::Tensor sorted_pairs,
+                       int64_t k);
+void moe_grouped_down(torch::Tensor ypair, torch::Tensor act, torch::Tensor w2,
+                      torch::Tensor topk_w, torch::Tensor expert_off,
+                      torch::Tensor sorted_pairs);
 void moe_gemm_gated_wq(torch::Tensor act, torch::Tensor x,
                        torch::Tensor w13_qs, torch::Tensor w13_d, int64_t bits,
                        torch::Tensor expert_off, torch::Tensor sorted_pairs,
@@ -218,6 +224,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Routed expert GEMM 2: ypair[p] = topk_w[p] * (act[p] @ w2_e^T), fp32");
   m.def("moe_combine", &moe_combine,
         "out[t] = bf16(sum over slots of ypair[t*k + j]), fixed order");
+  m.def("moe_grouped_gated", &moe_grouped_gated,
+        "moe_gemm_gated for prefill: grouped GEMM over the pair lists, "
+        "LDS-tiled, 64/128-pair row tiles");
+  m.def("moe_grouped_down", &moe_grouped_down,
+        "moe_gemm_down for prefill: grouped GEMM over the pair lists, "
+        "LDS-tiled, 64/128-pair row tiles");
   m.def("moe_gemm_gated_wq", &moe_gemm_gated_wq,
         "Routed expert GEMM 1 over Q4_0/Q8_0 expert planes, dequant fused "
         "into the MFMA loop");

@@ -1,18 +1,21 @@
 #!/usr/bin/env python
-"""Mixture-of-experts layer benchmark: the fused routed-GEMM kernels against
-the eager library path.
+"""Mixture-of-experts layer benchmark: the fused routed-GEMM kernels and
+the grouped prefill kernels against the eager library path.
 
-Times ops.moe_forward (route + lists + experts + combine) with fused=True
-and fused=False on one Mixtral-shaped MoE layer (E 8, k 2, H 4096, I 14336
-unless given) at decode and prefill token counts, under two routings:
+Times ops.moe_forward (route + lists + experts + combine) with fused=True,
+fused=False and (bf16 experts) fused="grouped" on one Mixtral-shaped MoE
+layer (E 8, k 2, H 4096, I 14336 unless given) at decode and prefill token
+counts (--t, repeatable; MOE_GROUPED_MIN_T's table is T = 128, 192, 256,
+384, 512, 1024, 2048, 4096), under two routings:
   uniform  random router logits
   skewed   every token's first choice is expert 0, the second one random
 and prints one JSON line per (T, routing, path): median and min
-microseconds per call, and for the fused path the bytes of the distinct
-activated experts' weights per second that time corresponds to.
+microseconds per call, the bytes of the distinct activated experts' weights
+per second that time corresponds to, and the expert GEMMs' 6*T*k*H*I
+floating-point operations per second.
 
 Method: device events around a window of `--iters` back-to-back calls,
-`--rounds` windows per path with the two paths interleaved inside one
+`--rounds` windows per path with the paths interleaved inside one
 process, after a warm-up of every shape. Each call uses the next of several
 copies of the layer's weights (more than the 256 MiB last-level cache
 between two uses of a weight), as consecutive layers of a model would. The
@@ -148,15 +151,18 @@ def main():
             counts = torch.bincount(ids.reshape(-1).long(), minlength=E)
             distinct = int((counts > 0).sum())
             paths = {"fused": True, "library": False}
+            if fmt == "bf16":
+                paths["grouped"] = "grouped"
             got = {}
             for name, fused in paths.items():               # warm-up
                 for i in range(2 * copies + 3):
                     got[name] = call(fused, x, logits, i)
             torch.cuda.synchronize()
-            # the two paths agree on what they compute (same weights: both
+            # the paths agree on what they compute (same weights: all
             # ended the warm-up on the same copy)
-            diff = (got["fused"].float() - got["library"].float()).abs().max()
             scale = got["library"].float().abs().max()
+            diff = {name: (o.float() - got["library"].float()).abs().max()
+                    for name, o in got.items()}
             times = {name: [] for name in paths}
             for _ in range(args.rounds):
                 for name, fused in paths.items():
@@ -180,9 +186,11 @@ def main():
                        "weight_bytes": distinct * expert_bytes,
                        "weight_GBps": round(
                            distinct * expert_bytes / med / 1e3, 1),
+                       "expert_TFLOPs": round(
+                           6 * T * k * H * I / med / 1e6, 1),
                        "speedup_vs_library": round(lib_med / med, 3),
                        "max_abs_diff_over_max": round(
-                           float(diff / scale), 5)}
+                           float(max(diff.values()) / scale), 5)}
                 line = json.dumps(rec)
                 print(line, flush=True)
                 lines.append(line)
