@@ -961,6 +961,33 @@ def moe_forward_wq(x: torch.Tensor, router_logits: torch.Tensor,
 # table for eager prefill above 128 tokens.
 MOE_KQ_FUSED_MAX_T = 128
 
+# Where moe_experts_kq(fused=None) takes the grouped prefill kernels
+# (ops/hip/moe_grouped_kq.hip; no host sync, capture-safe). The rule is
+# MOE_GROUPED_MIN_T's: the smallest benchmarked T (scripts/bench_moe.py --fmt
+# q4_k / q6_k, T = 128, 192, 256, 384, 512, 1024, 2048, 4096), never below
+# 193, from which the grouped path is slower than neither other K-quant path
+# (fused=True, fused=False) on uniform routing, for both formats, on the
+# Mixtral and the Qwen3-30B-A3B layer, in two runs; plus one if that T is a
+# member of graph_runner.BATCH_BUCKETS.
+# MEASURED, not the provisional 257 (profiles/r17_moe_grouped_kq.md): the
+# Qwen3-30B-A3B layer with q4_k decides. There the fused decode kernels are
+# still 2-7 % ahead of grouped at T = 128, 192 and 256 (306 against 312 us
+# at 256) and behind from 384 (378 against 342); q6_k turns at 256, the
+# Mixtral layer at 192 in both formats. 384 is a bucket, so 385. Against the
+# library path, which fused=None takes below the cutoff, grouped is 1.8-2.3x
+# (Mixtral) and 31-46x (Qwen3) faster at every T from 128 to 512: the rule
+# leaves that on the table for prefills of 129 to 384 tokens.
+# At the top the Mixtral layer repeats the bf16 result: from T = 1024 the
+# library path's eight large GEMMs win (grouped over library 0.98 / 0.81 /
+# 0.66 q4_k, 0.97 / 0.76 / 0.59 q6_k at 1024 / 2048 / 4096), so the window is
+# closed at MOE_KQ_GROUPED_MAX_T = 512 for layers with fewer than
+# MOE_KQ_GROUPED_ANY_T_MIN_E = 128 experts, the one expert count at which
+# grouped was measured ahead of both paths at every T from the cutoff on
+# (7.6x the library path at 4096). Expert counts in between were not measured.
+MOE_KQ_GROUPED_MIN_T = 385
+MOE_KQ_GROUPED_MAX_T = 512
+MOE_KQ_GROUPED_ANY_T_MIN_E = 128
+
 _MOE_KQ_NPLANES = {"q4_k": 2, "q6_k": 4}
 
 
@@ -1000,7 +1027,8 @@ def dequantize_experts_kq(planes, fmt: str,
 
 def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
                    topk_ids: torch.Tensor, topk_w: torch.Tensor,
-                   fused: bool | None = None, out: torch.Tensor | None = None,
+                   fused: bool | str | None = None,
+                   out: torch.Tensor | None = None,
                    act: torch.Tensor | None = None,
                    ypair: torch.Tensor | None = None,
                    scratch: torch.Tensor | None = None) -> torch.Tensor:
@@ -1011,13 +1039,19 @@ def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
     rows = H, K = I for w2. `fmt` is "q4_k" / "q6_k" or a (w13 format, w2
     format) pair; gate and up share a format.
     GPU, fused=True: moe_align + the two dequant-fused routed GEMM kernels +
-    moe_combine; capture-safe, any T. GPU, fused=False: the eager library
-    path (one host sync): per non-empty expert dequant_kq of w13[e]'s plane
+    moe_combine; capture-safe, any T. GPU, fused="grouped": the same with
+    the two grouped prefill kernels (moe_grouped_kq.hip), which dequantise
+    each weight tile into LDS once per row tile; bit-identical to
+    moe_experts(fused="grouped") on the dequantised stacks; no `scratch`.
+    GPU, fused=False: the eager library path (one host sync): per
+    non-empty expert dequant_kq of w13[e]'s plane
     slices into `scratch`, F.linear, silu_and_mul, dequant_kq of w2[e] into
     the same scratch (same stream, so ordered), F.linear; scaled into the
     same fp32 ypair, the same moe_combine. `scratch` is a contiguous bf16
     buffer of at least 2*I*H elements, allocated per call when None.
-    fused=None: fused up to MOE_KQ_FUSED_MAX_T tokens.
+    fused=None: fused up to MOE_KQ_FUSED_MAX_T tokens, grouped from
+    MOE_KQ_GROUPED_MIN_T tokens (up to MOE_KQ_GROUPED_MAX_T tokens when E <
+    MOE_KQ_GROUPED_ANY_T_MIN_E), the library path otherwise.
     CPU: moe_experts (the torch reference) on the stacks dequantised to
     bf16, the definition."""
     f13, f2 = _moe_kq_fmt_pair(fmt)
@@ -1039,7 +1073,14 @@ def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
             f"{tuple(topk_ids.shape)} and topk_w {tuple(topk_w.shape)} "
             f"disagree on [T, k]")
     if fused is None:
-        fused = T <= MOE_KQ_FUSED_MAX_T
+        if T >= MOE_KQ_GROUPED_MIN_T and (
+                T <= MOE_KQ_GROUPED_MAX_T or E >= MOE_KQ_GROUPED_ANY_T_MIN_E):
+            fused = "grouped"
+        else:
+            fused = T <= MOE_KQ_FUSED_MAX_T
+    if fused not in (True, False, "grouped"):
+        raise ValueError(f"moe_experts_kq: fused must be True, False, "
+                         f"'grouped' or None, got {fused!r}")
     if act is None:
         act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
     if ypair is None:
@@ -1050,7 +1091,10 @@ def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
     off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
     pairs = torch.empty(P, dtype=torch.int32, device=x.device)
     C.moe_align(off, pairs, topk_ids, E)
-    if fused:
+    if fused == "grouped":
+        C.moe_grouped_gated_kq(act, x, list(p13), f13, off, pairs, k)
+        C.moe_grouped_down_kq(ypair, act, list(p2), f2, topk_w, off, pairs)
+    elif fused:
         C.moe_gemm_gated_kq(act, x, list(p13), f13, off, pairs, k)
         C.moe_gemm_down_kq(ypair, act, list(p2), f2, topk_w, off, pairs)
     else:
@@ -1084,10 +1128,10 @@ def moe_experts_kq(x: torch.Tensor, w13_planes, w2_planes, fmt,
 
 def moe_forward_kq(x: torch.Tensor, router_logits: torch.Tensor,
                    w13_planes, w2_planes, fmt, k: int,
-                   fused: bool | None = None,
+                   fused: bool | str | None = None,
                    scratch: torch.Tensor | None = None) -> torch.Tensor:
     """One MoE MLP over K-quant experts: route (moe_route) and run the
-    routed experts (moe_experts_kq)."""
+    routed experts (moe_experts_kq; `fused` is passed through)."""
     ids, w = moe_route(router_logits, k)
     return moe_experts_kq(x, w13_planes, w2_planes, fmt, ids, w, fused=fused,
                           scratch=scratch)

@@ -136,6 +136,14 @@ void moe_gemm_down_kq(torch::Tensor ypair, torch::Tensor act,
                       torch::Tensor topk_w, torch::Tensor expert_off,
                       torch::Tensor sorted_pairs);
 int64_t moe_kq_waves(int64_t N, int64_t K, bool gated);
+void moe_grouped_gated_kq(torch::Tensor act, torch::Tensor x,
+                          std::vector<torch::Tensor> w13_planes,
+                          std::string fmt, torch::Tensor expert_off,
+                          torch::Tensor sorted_pairs, int64_t k);
+void moe_grouped_down_kq(torch::Tensor ypair, torch::Tensor act,
+                         std::vector<torch::Tensor> w2_planes, std::string fmt,
+                         torch::Tensor topk_w, torch::Tensor expert_off,
+                         torch::Tensor sorted_pairs);
 int64_t moe_max_experts();
 int64_t moe_max_topk();
 int64_t moe_chunk_pairs();
@@ -246,6 +254,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_kq_waves", &moe_kq_waves,
         "K-split factor (waves per workgroup) moe_gemm_*_kq uses for one "
         "expert's [N, K] weight");
+  m.def("moe_grouped_gated_kq", &moe_grouped_gated_kq,
+        "moe_gemm_gated_kq for prefill: grouped GEMM over the pair lists, "
+        "Q4_K/Q6_K weights dequantised into LDS");
+  m.def("moe_grouped_down_kq", &moe_grouped_down_kq,
+        "moe_gemm_down_kq for prefill: grouped GEMM over the pair lists, "
+        "Q4_K/Q6_K weights dequantised into LDS, fp32 ypair");
   m.attr("MOE_MAX_EXPERTS") = moe_max_experts();
   m.attr("MOE_MAX_TOPK") = moe_max_topk();
   m.attr("MOE_CHUNK_PAIRS") = moe_chunk_pairs();

@@ -3,8 +3,8 @@
 the grouped prefill kernels against the eager library path.
 
 Times ops.moe_forward (route + lists + experts + combine) with fused=True,
-fused=False and (bf16 experts) fused="grouped" on one Mixtral-shaped MoE
-layer (E 8, k 2, H 4096, I 14336 unless given) at decode and prefill token
+fused=False and (bf16, q4_k, q6_k experts) fused="grouped" on one
+Mixtral-shaped MoE layer (E 8, k 2, H 4096, I 14336 unless given) at decode and prefill token
 counts (--t, repeatable; MOE_GROUPED_MIN_T's table is T = 128, 192, 256,
 384, 512, 1024, 2048, 4096), under two routings:
   uniform  random router logits
@@ -31,7 +31,9 @@ session to compare them.
 --fmt q4_k | q6_k times ops.moe_forward_kq on the layer held as ggml
 Q4_K / Q6_K super-block planes (random payload and scale codes, small finite
 fp16 d / dmin); H and I must be multiples of 256. weight_bytes counts the
-super-blocks (144 / 210 bytes per 256 weights).
+super-blocks (144 / 210 bytes per 256 weights). The grouped path
+(moe_grouped_kq.hip) is the third interleaved variant, as for bf16;
+MOE_KQ_GROUPED_MIN_T's table is MOE_GROUPED_MIN_T's.
 
 A GPU is required; there is no CPU fallback. Run under a time limit, e.g.
     timeout 600 python scripts/bench_moe.py --out moe.jsonl
@@ -151,7 +153,7 @@ def main():
             counts = torch.bincount(ids.reshape(-1).long(), minlength=E)
             distinct = int((counts > 0).sum())
             paths = {"fused": True, "library": False}
-            if fmt == "bf16":
+            if fmt == "bf16" or kq:
                 paths["grouped"] = "grouped"
             got = {}
             for name, fused in paths.items():               # warm-up
