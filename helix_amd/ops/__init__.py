@@ -830,6 +830,41 @@ def moe_forward(x: torch.Tensor, router_logits: torch.Tensor,
 # was benchmarked.
 MOE_WQ_FUSED_MAX_T = 128
 
+# Where moe_experts_wq(fused=None) takes the grouped prefill kernels
+# (ops/hip/moe_grouped_wq.hip; no host sync, capture-safe). The rule is
+# MOE_GROUPED_MIN_T's: the smallest benchmarked T (scripts/bench_moe.py --fmt
+# q4_0 / q8_0, T = 128, 192, 256, 384, 512, 1024, 2048, 4096), never below
+# 193, from which the grouped path is slower than neither other path
+# (fused=True, fused=False) on uniform routing, for both formats, on the
+# Mixtral and the Qwen3-30B-A3B layer, in two runs; plus one if that T is a
+# member of graph_runner.BATCH_BUCKETS. MOE_WQ_GROUPED_MAX_T and
+# MOE_WQ_GROUPED_ANY_T_MIN_E close the window at the top as the K-quant pair
+# does: the largest benchmarked T at which grouped is not slower than the
+# library path on both layers, for layers with fewer experts than the one
+# count at which grouped was measured ahead at every T.
+# MEASURED, not the provisional 257 (profiles/r18_moe_grouped_wq.md), us
+# grouped / fused / library on uniform routing, q4_0, second run (the first
+# and q8_0 agree on every ordering):
+#   T        192            256            384            512
+#   Mixtral  710/814/1525   901/1102/1628  931/1591/1716  1337/2095/1752
+#   Qwen3    280/244/11657  298/281/11687  331/343/10748  363/410/10781
+# The Qwen3-30B-A3B layer decides: the fused decode kernels stay ahead of
+# grouped up to T = 256 (q8_0: 308 against 310 us) and fall behind from 384;
+# the Mixtral layer turns at 192. 384 is a bucket, so 385. Against the
+# library path, which fused=None takes below the cutoff, grouped is 1.8-2.2x
+# (Mixtral) and 32-47x (Qwen3) faster at every T from 128 to 384: the rule
+# leaves that on the table for prefills of 129 to 384 tokens, as the K-quant
+# one does. At the top the Mixtral layer repeats the bf16 and K-quant
+# result: from T = 1024 the library path's eight large GEMMs win (grouped
+# over library 0.95 / 0.76 / 0.64 q4_0, 0.96 / 0.78 / 0.65 q8_0 at 1024 /
+# 2048 / 4096), so the window is closed at 512 below 128 experts, the one
+# count at which grouped was ahead of both paths at every T from the cutoff
+# on (7.2x the library path at 4096). Expert counts in between were not
+# measured.
+MOE_WQ_GROUPED_MIN_T = 385
+MOE_WQ_GROUPED_MAX_T = 512
+MOE_WQ_GROUPED_ANY_T_MIN_E = 128
+
 
 def _moe_fmt_pair(fmt):
     f13, f2 = (fmt, fmt) if isinstance(fmt, str) else tuple(fmt)
@@ -850,7 +885,8 @@ def dequantize_experts_wq(qs: torch.Tensor, d: torch.Tensor, fmt: str,
 
 def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
                    topk_ids: torch.Tensor, topk_w: torch.Tensor,
-                   fused: bool | None = None, out: torch.Tensor | None = None,
+                   fused: bool | str | None = None,
+                   out: torch.Tensor | None = None,
                    act: torch.Tensor | None = None,
                    ypair: torch.Tensor | None = None,
                    scratch: torch.Tensor | None = None) -> torch.Tensor:
@@ -859,13 +895,19 @@ def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
     (qs [E, H, I/2 or I], d fp16 [E, H, I/32]); `fmt` is "q4_0" / "q8_0" or
     a (w13 format, w2 format) pair.
     GPU, fused=True: moe_align + the two dequant-fused routed GEMM kernels +
-    moe_combine; capture-safe, any T. GPU, fused=False: the eager library
+    moe_combine; capture-safe, any T. GPU, fused="grouped": the same with
+    the two grouped prefill kernels (moe_grouped_wq.hip), which dequantise
+    each weight tile into LDS once per row tile; bit-identical to
+    moe_experts(fused="grouped") on the dequantised stacks; no `scratch`.
+    GPU, fused=False: the eager library
     path (one host sync): per non-empty expert dequant_wq of w13[e] into
     `scratch`, F.linear, silu_and_mul, dequant_wq of w2[e] into the same
     scratch (same stream, so ordered), F.linear; scaled into the same fp32
     ypair, the same moe_combine. `scratch` is a contiguous bf16 buffer of at
     least 2*I*H elements, allocated per call when None. fused=None: fused
-    up to MOE_WQ_FUSED_MAX_T tokens.
+    up to MOE_WQ_FUSED_MAX_T tokens, grouped from MOE_WQ_GROUPED_MIN_T
+    tokens (up to MOE_WQ_GROUPED_MAX_T tokens when E <
+    MOE_WQ_GROUPED_ANY_T_MIN_E), the library path otherwise.
     CPU: moe_experts (the torch reference) on the stacks dequantised to
     bf16, the definition."""
     f13, f2 = _moe_fmt_pair(fmt)
@@ -889,7 +931,14 @@ def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
             f"{tuple(topk_ids.shape)} and topk_w {tuple(topk_w.shape)} "
             f"disagree on [T, k]")
     if fused is None:
-        fused = T <= MOE_WQ_FUSED_MAX_T
+        if T >= MOE_WQ_GROUPED_MIN_T and (
+                T <= MOE_WQ_GROUPED_MAX_T or E >= MOE_WQ_GROUPED_ANY_T_MIN_E):
+            fused = "grouped"
+        else:
+            fused = T <= MOE_WQ_FUSED_MAX_T
+    if fused not in (True, False, "grouped"):
+        raise ValueError(f"moe_experts_wq: fused must be True, False, "
+                         f"'grouped' or None, got {fused!r}")
     if act is None:
         act = torch.empty(P, I, dtype=torch.bfloat16, device=x.device)
     if ypair is None:
@@ -900,7 +949,11 @@ def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
     off = torch.empty(E + 1, dtype=torch.int32, device=x.device)
     pairs = torch.empty(P, dtype=torch.int32, device=x.device)
     C.moe_align(off, pairs, topk_ids, E)
-    if fused:
+    if fused == "grouped":
+        C.moe_grouped_gated_wq(act, x, q13, d13, wq_bits(f13), off, pairs, k)
+        C.moe_grouped_down_wq(ypair, act, q2, d2, wq_bits(f2), topk_w, off,
+                              pairs)
+    elif fused:
         C.moe_gemm_gated_wq(act, x, q13, d13, wq_bits(f13), off, pairs, k)
         C.moe_gemm_down_wq(ypair, act, q2, d2, wq_bits(f2), topk_w, off,
                            pairs)
@@ -935,10 +988,10 @@ def moe_experts_wq(x: torch.Tensor, w13_planes, w2_planes, fmt,
 
 def moe_forward_wq(x: torch.Tensor, router_logits: torch.Tensor,
                    w13_planes, w2_planes, fmt, k: int,
-                   fused: bool | None = None,
+                   fused: bool | str | None = None,
                    scratch: torch.Tensor | None = None) -> torch.Tensor:
     """One MoE MLP over quantised experts: route (moe_route) and run the
-    routed experts (moe_experts_wq)."""
+    routed experts (moe_experts_wq; `fused` is passed through)."""
     ids, w = moe_route(router_logits, k)
     return moe_experts_wq(x, w13_planes, w2_planes, fmt, ids, w, fused=fused,
                           scratch=scratch)

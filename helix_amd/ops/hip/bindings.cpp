@@ -127,6 +127,14 @@ void moe_gemm_down_wq(torch::Tensor ypair, torch::Tensor act,
                       torch::Tensor topk_w, torch::Tensor expert_off,
                       torch::Tensor sorted_pairs);
 int64_t moe_waves(int64_t N, int64_t K, bool gated);
+void moe_grouped_gated_wq(torch::Tensor act, torch::Tensor x,
+                          torch::Tensor w13_qs, torch::Tensor w13_d,
+                          int64_t bits, torch::Tensor expert_off,
+                          torch::Tensor sorted_pairs, int64_t k);
+void moe_grouped_down_wq(torch::Tensor ypair, torch::Tensor act,
+                         torch::Tensor w2_qs, torch::Tensor w2_d, int64_t bits,
+                         torch::Tensor topk_w, torch::Tensor expert_off,
+                         torch::Tensor sorted_pairs);
 void moe_gemm_gated_kq(torch::Tensor act, torch::Tensor x,
                        std::vector<torch::Tensor> w13_planes, std::string fmt,
                        torch::Tensor expert_off, torch::Tensor sorted_pairs,
@@ -246,6 +254,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_waves", &moe_waves,
         "K-split factor (waves per workgroup) moe_gemm uses for one expert's "
         "[N, K] weight");
+  m.def("moe_grouped_gated_wq", &moe_grouped_gated_wq,
+        "moe_gemm_gated_wq for prefill: grouped GEMM over the pair lists, "
+        "Q4_0/Q8_0 weights dequantised into LDS");
+  m.def("moe_grouped_down_wq", &moe_grouped_down_wq,
+        "moe_gemm_down_wq for prefill: grouped GEMM over the pair lists, "
+        "Q4_0/Q8_0 weights dequantised into LDS, fp32 ypair");
   m.def("moe_gemm_gated_kq", &moe_gemm_gated_kq,
         "Routed expert GEMM 1 over Q4_K/Q6_K expert planes, dequant fused "
         "into the MFMA loop");

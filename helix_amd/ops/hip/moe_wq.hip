@@ -29,7 +29,7 @@
 // No atomics, no accumulation across workgroups; a pair's bits do not
 // depend on T, on its place in its list or on its tile's neighbours.
 #include "dequant_common.h"
-#include "moe_common.h"
+#include "moe_wq_common.h"
 #include <ATen/hip/HIPContext.h>
 
 using namespace helix;
@@ -180,30 +180,6 @@ __global__ __launch_bounds__(W * WAVE) void moe_gemm_wq_kernel(
   }
 }
 
-// Contract of one expert stack's (qs, d) pair: returns E; sets rows and K.
-int64_t check_stack(const torch::Tensor& qs, const torch::Tensor& d,
-                    int64_t bits, const char* what, int64_t* rows_out,
-                    int64_t* K_out) {
-  TORCH_CHECK(bits == 4 || bits == 8, what, ": bits must be 4 or 8, got ",
-              bits);
-  TORCH_CHECK(qs.is_cuda(), what, ": qs must be on GPU");
-  TORCH_CHECK(qs.dim() == 3 && d.dim() == 3, what,
-              ": qs and d must be 3-D [E, rows, ...]");
-  check_tensor(qs, qs, bits == 4 ? torch::kUInt8 : torch::kInt8, what);
-  check_tensor(d, qs, torch::kFloat16, what);
-  const int64_t E = qs.size(0), rows = qs.size(1);
-  const int64_t K = bits == 4 ? qs.size(2) * 2 : qs.size(2);
-  TORCH_CHECK(K > 0 && K % 32 == 0, what, ": K (", K,
-              ") must be a positive multiple of 32");
-  TORCH_CHECK(d.size(0) == E && d.size(1) == rows && d.size(2) == K / 32,
-              what, ": d must be [E, rows, K/32] = [", E, ", ", rows, ", ",
-              K / 32, "]");
-  TORCH_CHECK(rows * K < (int64_t(1) << 31), what, ": expert too large");
-  *rows_out = rows;
-  *K_out = K;
-  return E;
-}
-
 template <int BITS, bool GATED, int MT>
 void launch_moe_gemm_wq(int waves, void* dst, const torch::Tensor& src,
                         const torch::Tensor& qs, const torch::Tensor& d,
@@ -277,8 +253,8 @@ void moe_gemm_gated_wq(torch::Tensor act, torch::Tensor x,
                        torch::Tensor expert_off, torch::Tensor sorted_pairs,
                        int64_t k) {
   int64_t rows = 0, H = 0;
-  const int64_t E = check_stack(w13_qs, w13_d, bits, "moe_gemm_gated_wq: w13",
-                                &rows, &H);
+  const int64_t E = check_stack_wq(w13_qs, w13_d, bits,
+                                   "moe_gemm_gated_wq: w13", &rows, &H);
   TORCH_CHECK(x.dim() == 2 && act.dim() == 2,
               "moe_gemm_gated_wq: x and act must be 2-D");
   const int64_t I = rows / 2;
@@ -307,8 +283,8 @@ void moe_gemm_down_wq(torch::Tensor ypair, torch::Tensor act,
                       torch::Tensor topk_w, torch::Tensor expert_off,
                       torch::Tensor sorted_pairs) {
   int64_t H = 0, I = 0;
-  const int64_t E = check_stack(w2_qs, w2_d, bits, "moe_gemm_down_wq: w2",
-                                &H, &I);
+  const int64_t E = check_stack_wq(w2_qs, w2_d, bits, "moe_gemm_down_wq: w2",
+                                   &H, &I);
   TORCH_CHECK(act.dim() == 2 && ypair.dim() == 2 && topk_w.dim() == 2,
               "moe_gemm_down_wq: act, ypair and topk_w must be 2-D");
   const int64_t T = topk_w.size(0), k = topk_w.size(1), P = T * k;

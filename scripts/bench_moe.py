@@ -3,7 +3,7 @@
 the grouped prefill kernels against the eager library path.
 
 Times ops.moe_forward (route + lists + experts + combine) with fused=True,
-fused=False and (bf16, q4_k, q6_k experts) fused="grouped" on one
+fused=False and fused="grouped" on one
 Mixtral-shaped MoE layer (E 8, k 2, H 4096, I 14336 unless given) at decode and prefill token
 counts (--t, repeatable; MOE_GROUPED_MIN_T's table is T = 128, 192, 256,
 384, 512, 1024, 2048, 4096), under two routings:
@@ -25,8 +25,10 @@ library path's host sync is inside its window: it is part of that path.
 Q4_0 / Q8_0 planes (random payload bytes and scales: the time does not
 depend on the values); its library path is the feature's own, with a
 dequantise per non-empty expert. weight_bytes then counts the blocks
-(18 / 34 bytes per 32 weights). Run bf16 and the quantised formats in one
-session to compare them.
+(18 / 34 bytes per 32 weights). The grouped path (moe_grouped_wq.hip) is
+the third interleaved variant; MOE_WQ_GROUPED_MIN_T's table is
+MOE_GROUPED_MIN_T's. Run bf16 and the quantised formats in one session to
+compare them.
 
 --fmt q4_k | q6_k times ops.moe_forward_kq on the layer held as ggml
 Q4_K / Q6_K super-block planes (random payload and scale codes, small finite
@@ -153,8 +155,7 @@ def main():
             counts = torch.bincount(ids.reshape(-1).long(), minlength=E)
             distinct = int((counts > 0).sum())
             paths = {"fused": True, "library": False}
-            if fmt == "bf16" or kq:
-                paths["grouped"] = "grouped"
+            paths["grouped"] = "grouped"
             got = {}
             for name, fused in paths.items():               # warm-up
                 for i in range(2 * copies + 3):
